@@ -2,7 +2,12 @@
 """Headline benchmark: keypoints/sec of the Sift::calculate() hot path on synthetic 1920x1080
 greyscale frames, 4 octaves x 3 DoGs (BASELINE.json metric / config 4's per-GPU share).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set-up, warm-up, the K timed steps, the result line (with the roofline
+figures that come from the timed steps' own events).  `--dump-outputs DIR` also writes what the last timed step returned.  `--full`
+adds every leg that takes runs of its own: repetitions of the K-step loop, the kernels alone on the chip, the host-buffer boundary,
+single-frame latency, the C++ drop-in, live PMC traffic, the CPU baseline with the parity spot check, the N > 1 gather check.
 
 One process per GPU (launched by torch.distributed.run for N > 1).  A "step" is one pass of the
 whole hot path (pyramid, DoG, extrema, edge filter, orientation, descriptors) over one batch of
@@ -51,6 +56,8 @@ GATHER_SETTLE_STEPS = 16
 PROFILE_EVERY = 4            # the events cost ~10 us per blur launch (0.16 ms per step): sample
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8 TB/s (spec)
 CPU_SAMPLE_FRAMES = 8
+DUMP_ROWS = 100000           # --dump-outputs: keypoints of the last timed step that are written (584 bytes each: 58 MB in all)
+DUMP_SEED = 20240229
 
 
 def host_cpu():
@@ -146,7 +153,7 @@ def pmc_traffic_live(extra_args):  # noqa: C901
         for c in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(tmp, c)
             cmd = [exe, "--pmc", c, "--kernel-trace", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-                   "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--pipeline-depth", "1"] + extra_args
+                   "--steps", "1", "--warmup", "1", "--pipeline-depth", "1"] + extra_args
             env = dict(os.environ, TMPDIR="/tmp")
             try:
                 r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=300)
@@ -298,6 +305,21 @@ def dropin_cpp_leg(frame, iterations=50):
         return {"error": repr(e)[:300]}
 
 
+def dump_outputs(path, counts, kp, desc):
+    """--dump-outputs: what the last timed step handed back (Context.counts() / Context.results() of the context that ran it), as
+    float arrays a later build's run with the same arguments can be compared with.  All per-image counts; of the keypoints a fixed,
+    seeded sample of rows (all of them up to DUMP_ROWS), the same rows of records and descriptors, in the order of the result."""
+    os.makedirs(path, exist_ok=True)
+    n = int(kp.shape[0])
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+    fields = ("x", "y", "octave", "index", "scale", "orientation", "filtered", "has_descriptor")
+    rec = np.stack([kp[f][rows].astype(np.float64) for f in fields], axis=1) if n else np.zeros((0, len(fields)))
+    np.save(os.path.join(path, "counts.npy"), np.asarray(counts, dtype=np.float64))
+    np.save(os.path.join(path, "sample_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "keypoints.npy"), rec)                     # columns: x, y, octave, index, scale, orientation, filtered, has_descriptor
+    np.save(os.path.join(path, "descriptors.npy"), np.ascontiguousarray(desc[rows], dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -307,12 +329,20 @@ def main():
     ap.add_argument("--workload", default="config4", choices=sorted(WORKLOADS),
                     help="config4 (default) is the headline workload; config3 / config5 are BASELINE.json's other GPU "
                          "configurations at their nearest non-throwing parameters (SURVEY 8(d)), reported as labelled extra lines")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (each takes runs of its own, after the timed steps): --repeats, the kernels alone on "
+                         "the chip (roofline.*_alone), host_inclusive, single_frame_ms, dropin_cpp, roofline.traffic, cpu_baseline + "
+                         "parity_spot_check, N > 1: gather_check.  Off by default: a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned to DIR/<name>.npy: counts (keypoints per image), keypoints "
+                         "(x, y, octave, index, scale, orientation, filtered, has_descriptor), descriptors (128 floats), sample_rows (which rows of the "
+                         f"result the two hold: all of them up to {DUMP_ROWS}, a fixed seeded sample beyond); N > 1: rank 0's own batch")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline / parity_spot_check leg")
     ap.add_argument("--profile-every", type=int, default=PROFILE_EVERY, help="every N-th batch of a context carries the per-launch timing events of the roofline figure")
     ap.add_argument("--host-loop", choices=("stream", "dispatch"), default="stream",
                     help="'stream' - each context's host thread takes its next step itself (N > 1: and packs its lists for the gather thread); "
                          "'dispatch' - one thread submits, collects and pushes to the gather (rounds 1 - 3)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the legs beside the headline: host-buffer rate, single-frame latency, live PMC traffic")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the host-buffer rate, single-frame latency, C++ drop-in and live PMC traffic legs")
     ap.add_argument("--pmc-traffic", type=int, default=1, choices=[0, 1],
                     help="1 (default): roofline.traffic is measured live by two child passes of this bench under rocprofv3 --pmc "
                          "(FETCH_SIZE / WRITE_SIZE, one step each); 0: traffic stays null")
@@ -331,9 +361,10 @@ def main():
     ap.add_argument("--rccl-loopback", action="store_true",
                     help="N = 1 only: every step's keypoint lists also travel through RCCL point-to-point to this same rank "
                          "(KeypointGather(loopback=True)): the N > 1 gather path, messages and sizes, on a one-GPU box")
-    ap.add_argument("--repeats", type=int, default=5, help="repetitions of the K-step loop reported as ms_per_step_repeats (the headline is the first)")
-    ap.add_argument("--check-gather", action="store_true", default=True,
-                    help="N > 1, after the timed region (the default since round 5: a multi-GPU line carries its own evidence): rank 0 runs every "
+    ap.add_argument("--repeats", type=int, default=None, help="repetitions of the K-step loop reported as ms_per_step_repeats (the headline is the first); "
+                                                               "default 5 with --full, 1 without")
+    ap.add_argument("--check-gather", action="store_true", default=None,
+                    help="N > 1, after the timed region (the default with --full: a multi-GPU line carries its own evidence): rank 0 runs every "
                          "rank's frames itself, rank by rank, and compares the lists that arrived through the gather in the last step with its "
                          "own - records, descriptor floats and per-image counts in global image order (seeds 1 .. N x frames); the line then "
                          "carries gather_check")
@@ -341,6 +372,10 @@ def main():
     ap.add_argument("--pipeline-gate", type=int, default=1, choices=[0, 1],
                     help="pipeline depth > 1: 1 (default) joins the contexts with a phase gate (sift_amd/csrc/phase_gate.h); 0 leaves the interleaving to the GPU's queues")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.check_gather is None:
+        args.check_gather = args.full
 
     global W, H, DOGS, OCTAVES, SUBPIXEL
     W, H, DOGS, OCTAVES, SUBPIXEL, frames_default, label = WORKLOADS[args.workload]
@@ -417,6 +452,7 @@ def main():
     tickets = []            # submitted steps whose results have not been collected yet (at most depth - 1 between steps)
 
     last_gathered = [None]  # the newest step that arrived on rank 0: (records_all, values_all, counts_all)
+    last_ctx = [None]       # the context that ran the newest step (--dump-outputs reads its results after the timed region)
 
     def note(done):
         for recs, vals, counts in done:
@@ -427,6 +463,7 @@ def main():
     def collect(ticket):
         """Finish one step: wait for its batch, hand its keypoint lists to the gather (N > 1), free its slot."""
         c = ticket.result()
+        last_ctx[0] = c
         total = c.total()
         if gatherer is not None:
             # wire format (lossless, sift_amd/gather.py): sparse = 34-byte records (20 + 112 presence bits) + the floats that are set
@@ -492,6 +529,8 @@ def main():
         def sink(c, slot, _item):
             total = c.total()
             per_slot[slot] += total
+            if seq_of[threading.get_ident()] == n_steps - 1:
+                last_ctx[0] = c     # (this context takes no further batch: the stream ends here)
             if gatherer is None:
                 return
             torch.cuda.set_device(local_rank)
@@ -547,6 +586,11 @@ def main():
     for c in ctxs:
         c.set_option("profile", 0)
     gathered_head = (gathered[0] - gatherer_t0[0], gathered[1] - gatherer_t0[1]) if gatherer is not None else (None, None)
+    if args.dump_outputs and rank == 0 and last_ctx[0] is not None:
+        # the last timed step's lists are still in its context (nothing has run on it since): fetched here, outside the timed region
+        kp_last, desc_last = last_ctx[0].results()
+        dump_outputs(args.dump_outputs, last_ctx[0].counts().copy(), kp_last, desc_last)
+        del kp_last, desc_last
     # the same K steps a few more times, AFTER the headline region (which stays the first repetition, so that `steps` and
     # `ms_per_step` describe one and the same loop): the spread of a 55 ms sample on this box, max over ranks each
     repeat_ms = [dt / args.steps * 1e3]
@@ -679,7 +723,7 @@ def main():
             out["config"]["gather_check"] = bool(ok)
             out["config"]["gather_check_what"] = (f"the last step's lists on rank 0 (records, descriptor floats, counts of {world * nf} images) equal "
                                                   f"rank 0's own run of every rank's frames, seeds 1..{world * nf} in order")
-        if world == 1:
+        if world == 1 and args.full:
             # ---- the blur family ALONE on the chip: a few steps one at a time after the timed region, every one instrumented
             ctx.set_option("profile", 1)
             ctx.profile_reset()
@@ -700,7 +744,7 @@ def main():
                 out["roofline"]["frac_alone"] = out["roofline"]["achieved_alone"] / HBM_PEAK_GBS
                 out["roofline"]["alone_what"] = ("the same events and bytes over 3 steps run one at a time AFTER the timed region: the blur launches alone on the chip "
                                                  "(in the timed region the previous step's cleanup chain shares the chip with them, phase gate schedule 1)")
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             # ---- the boundary as a host caller sees it (main.cpp:56-57 hands over host memory and reads the vector back):
             # frames from host memory in, keypoints + descriptors to host memory out, two batches in flight
             from sift_amd.sift import pinned_array
@@ -802,7 +846,7 @@ def main():
                 traffic, src = pmc_traffic_live(extra)
                 out["roofline"]["traffic"] = traffic
                 out["roofline"]["traffic_source"] = src
-        if world == 1 and not args.no_cpu_baseline and args.workload == "config4":
+        if world == 1 and args.full and not args.no_cpu_baseline and args.workload == "config4":
             out["cpu_baseline"] = cpu_baseline(frames[:CPU_SAMPLE_FRAMES])
             # ---- result check of this very run, outside the timed region: one more step of the batch through the same pipeline,
             # its first CPU_SAMPLE_FRAMES images' keypoints and descriptors against what the oracle just computed for those frames

@@ -500,6 +500,44 @@ def test_bench_rccl_loopback_prints_one_line():
     assert out["config"]["gather_steps_on_rank0"] >= 3 and out["value"] > 0
 
 
+def test_bench_plain_run_dumps_the_last_steps_outputs(ctx, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` does the timed steps only (the legs with runs of their own wait behind
+    `--full`), and `--dump-outputs DIR` writes what the last timed step returned as float arrays: here they must be what a
+    context of this process returns for the same frames (seeds 1 and 2), row for row, bit for bit."""
+    import subprocess
+    import sys
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    dump = str(tmp_path / "dump")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--frames", "2",
+                        "--dump-outputs", dump], env=env, cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["unit"] == "keypoints/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["ms_per_step"] > 0 and abs(out["value"] - out["config"]["keypoints_per_step"] / (out["ms_per_step"] * 1e-3)) <= 1e-6 * out["value"]
+    assert out["ms_per_step_repeats"]["n"] == 1
+    for key in ("cpu_baseline", "parity_spot_check", "host_inclusive", "single_frame_ms", "dropin_cpp"):
+        assert key not in out, key
+    assert "frac_alone" not in out["roofline"] and out["roofline"]["traffic"] is None and out["roofline"]["frac"] > 0
+
+    got = {n: np.load(os.path.join(dump, n + ".npy")) for n in ("counts", "sample_rows", "keypoints", "descriptors")}
+    assert sorted(os.listdir(dump)) == sorted(n + ".npy" for n in got)
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(os.path.getsize(os.path.join(dump, f)) for f in os.listdir(dump)) <= 64 * 1000 * 1000
+    frames = np.stack([synth_frame(1920, 1080, s) for s in (1, 2)])
+    ctx.calculate_batch(frames, _lib.Params(3, 4, 1.6, O.K_SQRT2, 0))
+    kp, desc = ctx.results()
+    assert np.array_equal(got["counts"], ctx.counts().astype(np.float64))
+    assert kp.size == out["config"]["keypoints_per_step"] and kp.size > 0
+    rows = got["sample_rows"].astype(np.int64)
+    assert np.array_equal(rows, np.arange(kp.size))      # fewer keypoints than the sample holds: every row is there
+    for col, f in enumerate(("x", "y", "octave", "index", "scale", "orientation", "filtered", "has_descriptor")):
+        assert got["keypoints"][:, col].astype(kp.dtype[f]).tobytes() == np.ascontiguousarray(kp[f][rows]).tobytes(), f
+    assert got["descriptors"].dtype == np.float32 and got["descriptors"].tobytes() == np.ascontiguousarray(desc[rows]).tobytes()
+
+
 @pytest.mark.parametrize("host_loop", ["stream", "dispatch"])
 def test_bench_eight_ranks_sharing_the_gpu(host_loop):
     """BASELINE config 4's world size on this one-GPU box: `bench.py --gpus 8` with all eight ranks on GPU 0 (gloo as the

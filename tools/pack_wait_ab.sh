@@ -1,4 +1,4 @@
-run() { timeout 600 python3 bench.py --steps 40 --warmup 4 --no-cpu-baseline --no-extras "$@" 2>/dev/null | python3 -c "
+run() { timeout 600 python3 bench.py --full --steps 40 --warmup 4 --no-cpu-baseline --no-extras "$@" 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads([ln for ln in sys.stdin.read().splitlines() if ln.startswith('{')][-1]); c = d['config']
 print('$LABEL $*', '->', round(d['ms_per_step'], 3), 'ms/step', [round(x,3) for x in d['ms_per_step_repeats']['all']], 'gather ms/step', c['gather_ms_per_step'])"; }

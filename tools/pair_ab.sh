@@ -3,7 +3,7 @@
 #   bash tools/pair_ab.sh [rounds] > gpurun_out/pair_ab.txt
 cd "$(dirname "$0")/.."
 rounds=${1:-2}
-line() { python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline "$@" 2>/dev/null | grep '^{' | python3 -c '
+line() { python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline "$@" 2>/dev/null | grep '^{' | python3 -c '
 import json, sys
 d = json.loads(sys.stdin.read())
 print("%.3f ms/step  repeats %s" % (d["ms_per_step"], " ".join("%.3f" % v for v in d["ms_per_step_repeats"]["all"])))'; }

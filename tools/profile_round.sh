@@ -8,20 +8,21 @@ O=gpurun_out/$R
 rm -rf $O; mkdir -p $O
 rocminfo 2>/dev/null | grep -m2 -E "gfx|Marketing" > $O/device.txt; lscpu | grep -E "Model name|^CPU\(s\)" >> $O/device.txt
 # 1. default bench under the kernel trace (same command as the stats in profiles/README.md)
-rm -rf gpurun_out/prof
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -- python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_profiled.json 2> /dev/null
-f=$(find gpurun_out/prof -name "*kernel_stats.csv" | head -1); cp "$f" $O/kernel_stats.csv
-t=$(find gpurun_out/prof -name "*kernel_trace.csv" | head -1)
+rm -rf $O/prof
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_profiled.json 2> /dev/null
+f=$(find $O/prof -name "*kernel_stats.csv" | head -1); cp "$f" $O/kernel_stats.csv
+t=$(find $O/prof -name "*kernel_trace.csv" | head -1)
 python3 tools/roofline_from_stats.py --stats $O/kernel_stats.csv > $O/roofline.txt
 python3 tools/roofline_from_stats.py --trace "$t" --dump $O/blur_launches.csv >> $O/roofline.txt
 python3 tools/timeline_window.py "$t" 8000 12500 > $O/timeline_pipelined.txt 2>&1   # (the last ~11 ms of the run are the three stand-alone steps)
+rm -rf $O/prof
 # 2. one step at a time: per-kernel timeline
 rm -rf gpurun_out/prof
 timeout 900 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/prof -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --pipeline-depth 1 > /dev/null 2>&1
 t=$(find gpurun_out/prof -name "*kernel_trace.csv" | head -1); python3 tools/timeline.py "$t" > $O/timeline_single_step.txt 2>&1
 rm -rf gpurun_out/prof
 # 3. unprofiled bench lines
-timeout 900 python3 bench.py --steps 20 --warmup 5 > $O/bench.json 2> /dev/null
+timeout 900 python3 bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> /dev/null
 timeout 600 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras --pipeline-depth 1 > $O/bench_depth1.json 2> /dev/null
 timeout 600 python3 bench.py --workload config3 --steps 5 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_config3.json 2> /dev/null
 timeout 600 python3 bench.py --workload config5 --steps 5 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_config5.json 2> /dev/null

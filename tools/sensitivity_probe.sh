@@ -4,7 +4,7 @@
 #   bash tools/sensitivity_probe.sh > gpurun_out/sens.txt
 cd "$(dirname "$0")/.."
 export SIFT_HIP_LIBRARY="$PWD/sift_amd/lib/libsift_hip_ablate.so"
-line() { python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline "$@" 2>/dev/null | grep '^{' | python3 -c '
+line() { python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline "$@" 2>/dev/null | grep '^{' | python3 -c '
 import json, sys
 d = json.loads(sys.stdin.read())
 print("%.3f ms/step  repeats %s  frac %.3f" % (d["ms_per_step"], " ".join("%.3f" % v for v in d["ms_per_step_repeats"]["all"]), d["roofline"]["frac"]))'; }
