@@ -190,6 +190,48 @@ int sift_hip_sparse_unpack(sift_hip_ctx* ctx, const void* dev_records, const voi
 int sift_hip_image_dims(sift_hip_ctx* ctx, int* w, int* h);
 int sift_hip_image_copy(sift_hip_ctx* ctx, int image, float* out);
 
+/* ---- descriptor matching (an extension: the reference has no matcher) ------------------------------------
+ * Descriptor rows are 128 floats.  For a query row a and a train row b, bit for bit:
+ *   dot(a,b) = fmaf(a[127], b[127], ... fmaf(a[1], b[1], fmaf(a[0], b[0], +0.0f)))   k ascending, one accumulator
+ *   n(a) = dot(a,a);  s = n(a) + n(b);  v = s - 2.0f * dot(a,b);  d2 = (v < 0.0f) ? 0.0f : v      (a NaN stays a NaN)
+ * d2 is symmetric and d2(a,a) == 0.  A candidate (d2, j) takes part when d2 is not a NaN and both rows are valid (no
+ * keypoint array given, or the row's has_descriptor != 0).  The best and the second best train row of a query row are the
+ * first two candidates in the order of (d2, j): the lower index wins a tie.  A missing entry is index -1, distance +inf.
+ * The distances run on the f32 matrix instruction of gfx950, which IS that fmaf chain; the result does not depend on
+ * tile sizes, on how a train set is split over workgroups or on the launch shape, and no nq x nt matrix is ever stored.
+ *
+ * Sets: `desc` (and `kp`, which may be NULL: every row valid) hold n_sets sets back to back, set s = rows offsets[s] ..
+ * offsets[s+1] - 1 (offsets: n_sets + 1 entries, host memory, ascending from >= 0).  Pairs: pair p matches the rows of set
+ * pair_q[p] (query) against those of set pair_t[p] (train); the same set on both sides is allowed (every row then finds
+ * itself first).  The pair arrays are host memory; desc, kp and the result arrays may each be host or device memory.
+ * Indices are relative to their set.  Empty sets are legal.  All pairs of a call share one launch of each kernel.
+ * The calls run on the context's stream and return when the results are in place; not while a batch of the context is in
+ * flight.  Scratch memory is allocated by the first match call of a context and kept with it. */
+typedef struct sift_hip_match_params {
+    float ratio;          /* 0: no ratio test; else 0 < ratio <= 1: keep when d2_best < (ratio * ratio) * d2_second */
+    uint8_t cross_check;  /* keep a row only if it is the best query row of its best train row (same order, same query set) */
+    uint8_t reserved[3];
+} sift_hip_match_params;
+typedef struct sift_hip_match_rec {
+    int32_t query, train; /* rows of the pair's query / train set */
+    float dist2, second2; /* d2 of the best and of the second best (+inf: none) */
+} sift_hip_match_rec;
+/* Top-2 of every query row: idx[rows][2], dist2[rows][2], rows = the query rows of the pairs, concatenated in pair order. */
+int sift_hip_knn2(sift_hip_ctx* ctx, const float* desc, const sift_hip_keypoint* kp, int n_sets, const int64_t* offsets,
+                  int n_pairs, const int32_t* pair_q, const int32_t* pair_t, int32_t* idx, float* dist2, char* err, int errlen);
+/* The filtered matches: records in pair order, then query order, densely packed into `recs`, which holds one record per
+ * query row of the pairs (the upper bound); counts[p] (host, may be NULL) = records of pair p, *total (host, may be NULL)
+ * their sum.  SIFT_HIP_EINVAL for a ratio outside [0, 1]. */
+int sift_hip_match(sift_hip_ctx* ctx, const float* desc, const sift_hip_keypoint* kp, int n_sets, const int64_t* offsets,
+                   int n_pairs, const int32_t* pair_q, const int32_t* pair_t, const sift_hip_match_params* params,
+                   sift_hip_match_rec* recs, int32_t* counts, int64_t* total, char* err, int errlen);
+/* The same over the images of the context's last batch: pair_q / pair_t are image indices, the sets are the images' rows of
+ * the device-resident result arrays (has_descriptor of their keypoints decides validity); nothing but the match list leaves
+ * the GPU.  SIFT_HIP_EINVAL when the context holds no results or an index is out of range. */
+int sift_hip_result_match(sift_hip_ctx* ctx, int n_pairs, const int32_t* pair_q, const int32_t* pair_t,
+                          const sift_hip_match_params* params, sift_hip_match_rec* recs, int32_t* counts, int64_t* total,
+                          char* err, int errlen);
+
 /* ---- inspection of the last batch (parity tests) ------------------------------------------------ */
 /* kind: 0 gaussian (levels 0..D), 1 dog (0..D-1), 2 magnitude, 3 orientation (initial gradient
  * maps, sift.cpp:130-160, only for levels some keypoint scale selects; 0x0 otherwise). */

@@ -35,6 +35,7 @@ SYMBOLS = [
     "sift_hip_result_copy_sparse", "sift_hip_sparse_unpack_host",
     "sift_hip_image_info", "sift_hip_image_read_band0", "sift_hip_image_read_bgr8", "sift_hip_png_write_bgr8",
     "sift_hip_rotated_rect_points", "sift_hip_overlay_box", "sift_hip_overlay_draw",
+    "sift_hip_knn2", "sift_hip_match", "sift_hip_result_match",
 ]
 
 
@@ -42,6 +43,13 @@ class Params(C.Structure):
     _fields_ = [("dogs_per_epoch", C.c_uint16), ("octaves", C.c_uint16), ("sigma", C.c_float),
                 ("k", C.c_float), ("subpixel", C.c_uint8), ("reserved", C.c_uint8 * 3)]
 
+
+class MatchParams(C.Structure):
+    _fields_ = [("ratio", C.c_float), ("cross_check", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("dist2", "<f4"), ("second2", "<f4")])
+assert MATCH_DTYPE.itemsize == 16
 
 KEYPOINT_DTYPE = np.dtype([("scale", "<f4"), ("orientation", "<f4"), ("x", "<u2"), ("y", "<u2"),
                            ("octave", "<u2"), ("index", "<u2"), ("filtered", "u1"),
@@ -169,5 +177,10 @@ def load():
     L.sift_hip_overlay_box.argtypes = [vp, ci, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), ip, fp]
     L.sift_hip_overlay_box.restype = None
     L.sift_hip_overlay_draw.argtypes = [u8p, ci, ci, vp, ll, ci]
+    i64p = np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")
+    # desc, kp and the result arrays may be host or device memory: plain addresses
+    L.sift_hip_knn2.argtypes = [vp, vp, vp, ci, i64p, ci, i32p, i32p, vp, vp, cs, ci]
+    L.sift_hip_match.argtypes = [vp, vp, vp, ci, i64p, ci, i32p, i32p, C.POINTER(MatchParams), vp, i32p, C.POINTER(C.c_int64), cs, ci]
+    L.sift_hip_result_match.argtypes = [vp, ci, i32p, i32p, C.POINTER(MatchParams), vp, i32p, C.POINTER(C.c_int64), cs, ci]
     _lib = L
     return L

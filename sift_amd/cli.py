@@ -2,6 +2,7 @@
 overlay :59-76) on top of the GPU path — SURVEY.md §8(f) rows 1-3.
 
     python -m sift_amd.cli -i image.pgm [-s 1.6] [-k 1.41421354] [-o 4] [-d 3] [-p 0] [-r 1]
+    python -m sift_amd.cli -i a.pgm --match b.pgm [--ratio 0.8] [--cross-check]      (an extension: matches.txt)
 
 Image ingest follows Vigra's scalar import: band 0 of multi-band files, values unscaled.  PGM,
 PPM, PNG and JPEG are decoded by the library itself (sift_amd/csrc/image_io.cpp, jpeg_decode.cpp: no PIL, no OpenCV, no libjpeg).
@@ -102,6 +103,20 @@ def draw_overlay(src_path: str, points, subpixel: bool, dst_path: str) -> None:
     _err_call(L.sift_hip_png_write_bgr8, dst_path.encode(), img.reshape(-1), w, h)
 
 
+def write_matches(path: str, matches) -> None:
+    """One line per match: query train dist2 second2 (positions in the two point lists, squared distances)."""
+    with open(path, "w") as out:
+        for m in matches:
+            out.write("%d %d %.9g %.9g\n" % (int(m["query"]), int(m["train"]), float(m["dist2"]), float(m["second2"])))
+
+
+def _load(path: str) -> np.ndarray:
+    img = read_image(path)
+    if image_info(path)[3] == 8:
+        img = img.astype(np.uint8)     # an 8-bit file: its samples cross the link as bytes, the GPU widens them to the same floats
+    return img
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="sift", description="SIFT features on the GPU (snowiow/SIFT options)")
     ap.add_argument("img_pos", nargs="?", help="image (positional, like the reference)")
@@ -113,15 +128,16 @@ def main(argv=None) -> int:
     ap.add_argument("--subpixel", "-p", type=int, default=0)
     ap.add_argument("--result", "-r", type=int, default=0)
     ap.add_argument("--no-overlay", action="store_true", help="skip <img>_orientation.png")
+    ap.add_argument("--match", metavar="IMG2", help="also run IMG2 and write the matches of the image's points among IMG2's to matches.txt")
+    ap.add_argument("--ratio", type=float, default=0.8, help="ratio test of --match (0: none)")
+    ap.add_argument("--cross-check", action="store_true", help="--match keeps mutual best matches only")
     args = ap.parse_args(argv)
     path = args.img or args.img_pos
     if not path:
         ap.print_help()
         return 1
     try:
-        img = read_image(path)
-        if image_info(path)[3] == 8:
-            img = img.astype(np.uint8)     # an 8-bit file: its samples cross the link as bytes, the GPU widens them to the same floats
+        img = _load(path)
         sift = Sift(args.dogsPerEpoch, args.octaves, args.sigma, args.k, bool(args.subpixel))
         points = sift.calculate(img)
         if not args.no_overlay:
@@ -129,6 +145,11 @@ def main(argv=None) -> int:
         if args.result:
             write_result("interstpoints.txt", points)
         print(f"{len(points)} interest points")
+        if args.match:
+            points2 = sift.calculate(_load(args.match))
+            matches = sift.match(points, points2, args.ratio, args.cross_check)
+            write_matches("matches.txt", matches)
+            print(f"{len(points2)} interest points in {args.match}, {len(matches)} matches")
     except (PreconditionViolation, AssertionError, RuntimeError, OSError) as ex:  # main.cpp:90-92
         print(ex, file=sys.stderr)
     return 0

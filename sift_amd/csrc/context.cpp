@@ -19,6 +19,7 @@
 #include "common.h"
 #include "phase_gate.h"
 #include "host_glue.h"
+#include "match_kernels.h"
 
 using namespace sift_hip;
 
@@ -204,6 +205,7 @@ struct sift_hip_ctx {
     double prof_bytes[kProfClasses] = {0, 0, 0, 0, 0};
     double prof_busy_ms[kProfClasses] = {0, 0, 0, 0, 0};   // time during which at least one launch of the class was running (union of the launches' intervals)
     long long prof_batches = 0;           // batches whose launches carried the events since the last reset
+    sift_hip::MatchState* match_state = nullptr;   // the matcher's scratch (match.cpp), made by the first match call
 };
 
 namespace {
@@ -1268,6 +1270,28 @@ int guarded(char* err, int errlen, F&& f) {
 
 }  // namespace
 
+// what match.cpp sees of a context (match_kernels.h)
+namespace sift_hip {
+MatchCtxView match_ctx_view(sift_hip_ctx* c) {
+    return MatchCtxView{c->device, c->stream, c->have_result, c->d_kp.as<sift_hip_keypoint>(), c->d_desc.as<float>(),
+                        c->counts.data(), (int)c->counts.size(), &c->match_state};
+}
+bool match_ptr_on_device(const void* p) {
+    hipPointerAttribute_t a;
+    std::memset(&a, 0, sizeof(a));
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
+}
+void match_upload(sift_hip_ctx* c, void* dev, const void* host, size_t bytes) { upload(c, dev, host, bytes, c->stream); }
+void match_download(sift_hip_ctx* c, void* dst, const void* dev, size_t bytes) { download(c, dst, dev, bytes, c->stream); }
+void match_wait(sift_hip_ctx* c) { wait_stream(c, c->stream); }
+int match_guarded(char* err, int errlen, int (*fn)(void*), void* arg) { return guarded(err, errlen, [&]() { return fn(arg); }); }
+void match_set_err(char* err, int errlen, const char* msg) { set_err(err, errlen, msg); }
+}  // namespace sift_hip
+
 // =====================================================================================================
 // Contexts that run batches side by side need hardware queues of their own: with the HIP runtime's default of 4, streams
 // of different contexts share a queue and inherit each other's ordering (the phase gate then loses what it arranges).
@@ -1313,6 +1337,7 @@ int sift_hip_create(int device, sift_hip_ctx** out, char* err, int errlen) {
             if (device < 64 && !touched[device]) {
                 tu_touch_pyramid(c->stream); tu_touch_pair(c->stream); tu_touch_reduce(c->stream); tu_touch_extrema(c->stream); tu_touch_orient(c->stream);
                 tu_touch_desc(c->stream); tu_touch_cleanup(c->stream); tu_touch_wire(c->stream); tu_touch_io(c->stream);
+                tu_touch_match(c->stream);
                 SIFT_HIP_CHECK(hipGetLastError());
                 SIFT_HIP_CHECK(hipStreamSynchronize(c->stream));
                 touched[device] = true;
@@ -1328,6 +1353,7 @@ void sift_hip_destroy(sift_hip_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     (void)sift_hip_set_gate(c, nullptr);
+    match_state_free(c->match_state);
     ApiGuard api;
     for (DevBuf* b : {&c->arena, &c->d_plan, &c->d_taps, &c->d_luts, &c->d_taps16, &c->d_input, &c->d_input_u8, &c->d_sparse_rec, &c->d_sparse_val, &c->d_base, &c->d_tmp, &c->d_tmp2,
                       &c->d_wk, &c->d_wi, &c->d_wi2, &c->d_wp, &c->d_status, &c->d_pool, &c->d_order, &c->d_masks, &c->d_fmasks, &c->d_counts, &c->d_tile_counts, &c->d_totals, &c->d_cands, &c->d_flags, &c->d_list, &c->d_list_cnt, &c->d_orient,

@@ -1,6 +1,7 @@
 // CPU build of the product's scalar math headers (the same code the HIP kernels inline), so the
 // `-m "not gpu"` tests can check them against libm and against the oracle without a GPU.
 // Not part of libsift_hip.so and never used by the product path.
+#include <math.h>
 #include <stdint.h>
 
 #include "fdlibm_atan2f.h"
@@ -72,5 +73,39 @@ long long hostmath_hist8_bin_mismatches(unsigned long long first, unsigned long 
 }
 float hostmath_vertex_parabola(uint16_t lnx, float lny, uint16_t px, float py, uint16_t rnx, float rny) {
     return sift_hip::vertex_parabola(lnx, lny, px, py, rnx, rny);
+}
+// Descriptor matching as include/sift_hip.h defines it, in plain loops: what the GPU matcher must reproduce bit for bit.
+// q: nq x 128, t: nt x 128, q_valid / t_valid: one byte per row or NULL (all valid); idx: nq x 2, dist2: nq x 2.
+static float match_dot(const float* a, const float* b) {
+    float acc = 0.0f;
+    for (int k = 0; k < 128; ++k) acc = fmaf(a[k], b[k], acc);
+    return acc;
+}
+void hostmath_match_knn2(const float* q, const uint8_t* q_valid, long long nq, const float* t, const uint8_t* t_valid, long long nt,
+                         int32_t* idx, float* dist2) {
+    float* tn = new float[nt > 0 ? nt : 1];
+    for (long long j = 0; j < nt; ++j) tn[j] = match_dot(t + j * 128, t + j * 128);
+    for (long long i = 0; i < nq; ++i) {
+        float d1 = INFINITY, d2 = INFINITY;
+        int32_t i1 = -1, i2 = -1;
+        if (!q_valid || q_valid[i]) {
+            const float na = match_dot(q + i * 128, q + i * 128);
+            for (long long j = 0; j < nt; ++j) {   // j ascending: a later row replaces an earlier one only when strictly nearer
+                if (t_valid && !t_valid[j]) continue;
+                const float s = na + tn[j];
+                const float v = s - 2.0f * match_dot(q + i * 128, t + j * 128);
+                const float d = (v < 0.0f) ? 0.0f : v;
+                if (d != d) continue;
+                if (i1 < 0 || d < d1) {
+                    d2 = d1; i2 = i1; d1 = d; i1 = (int32_t)j;
+                } else if (i2 < 0 || d < d2) {
+                    d2 = d; i2 = (int32_t)j;
+                }
+            }
+        }
+        idx[2 * i] = i1; idx[2 * i + 1] = i2;
+        dist2[2 * i] = d1; dist2[2 * i + 1] = d2;
+    }
+    delete[] tn;
 }
 }

@@ -1,0 +1,301 @@
+// Host side of descriptor matching (include/sift_hip.h: sift_hip_knn2, sift_hip_match, sift_hip_result_match): staging of
+// caller memory, the tile table that makes many pairs one launch, and the scratch memory, which the first match call of a
+// context allocates and the context keeps - outside the batch arena, so a context that never matches allocates nothing here.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "common.h"
+#include "match_kernels.h"
+
+namespace sift_hip {
+
+namespace {
+struct Buf {   // device memory that only grows
+    void* p = nullptr;
+    size_t cap = 0;
+    void ensure(size_t bytes) {
+        if (bytes <= cap) return;
+        ApiGuard api;
+        if (p) SIFT_HIP_CHECK(hipFree(p));
+        p = nullptr;
+        cap = 0;
+        SIFT_HIP_CHECK(hipMalloc(&p, bytes + bytes / 4));
+        cap = bytes + bytes / 4;
+    }
+    void release() {
+        ApiGuard api;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <class T>
+    T* as() const { return reinterpret_cast<T*>(p); }
+};
+}  // namespace
+
+struct MatchState {
+    Buf d_desc, d_kp;                 // staging of descriptor rows / keypoint records that arrive in host memory
+    Buf d_norm, d_valid;              // n(a) and the valid flag of every row
+    Buf d_tiles, d_blocks, d_pairs;   // the launch tables
+    Buf d_part;                       // partial top-2s, kMatchQ per tile
+    Buf d_idx, d_dist;                // top-2 of every query row (forward rows first, then the cross-check's reverse rows)
+    Buf d_seg, d_out, d_counts;       // records per pair segment, the dense list, per-pair counts
+    void* h_tables = nullptr;         // page-locked image of the three tables (the copy is asynchronous)
+    size_t h_cap = 0;
+    std::vector<int32_t> counts;
+};
+
+void match_state_free(MatchState* st) {
+    if (!st) return;
+    for (Buf* b : {&st->d_desc, &st->d_kp, &st->d_norm, &st->d_valid, &st->d_tiles, &st->d_blocks, &st->d_pairs, &st->d_part, &st->d_idx,
+                   &st->d_dist, &st->d_seg, &st->d_out, &st->d_counts})
+        b->release();
+    if (st->h_tables) {
+        ApiGuard api;
+        (void)hipHostFree(st->h_tables);
+    }
+    delete st;
+}
+
+namespace {
+
+struct Job {
+    sift_hip_ctx* c;
+    const float* desc;
+    const sift_hip_keypoint* kp;
+    bool inputs_on_device;   // sift_hip_result_match: the context's own arrays
+    int n_sets;
+    const int64_t* offsets;
+    int n_pairs;
+    const int32_t *pair_q, *pair_t;
+    const sift_hip_match_params* params;   // null: top-2 only
+    int32_t* idx;
+    float* dist2;
+    sift_hip_match_rec* recs;
+    int32_t* counts;
+    int64_t* total;
+    char* err;
+    int errlen;
+};
+
+int fail(const Job& j, const char* msg) {
+    match_set_err(j.err, j.errlen, msg);
+    return SIFT_HIP_EINVAL;
+}
+
+size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+
+// the tiles of one (query set, train set): blocks of kMatchQ query rows, each against `splits` ranges of the train set
+void add_tiles(long long q0, long long nq, long long t0, long long nt, int target_tiles_per_block, int out_row0, std::vector<MatchTile>& tiles,
+               std::vector<MatchBlock>& blocks) {
+    const long long stages = (nt + kMatchT - 1) / kMatchT;
+    const long long stages_per_split_min = kMatchSplitRows / kMatchT;
+    long long splits = std::max<long long>(1, std::min<long long>(target_tiles_per_block, (nt + kMatchSplitRows - 1) / kMatchSplitRows));
+    long long per = (stages + splits - 1) / std::max<long long>(splits, 1);
+    per = (per + stages_per_split_min - 1) / stages_per_split_min * stages_per_split_min;   // split edges at multiples of kMatchSplitRows
+    for (long long b = 0; b * kMatchQ < nq; ++b) {
+        MatchBlock blk{};
+        blk.q_row0 = (int)(q0 + b * kMatchQ);
+        blk.q_rows = (int)std::min<long long>(kMatchQ, nq - b * kMatchQ);
+        blk.out_row0 = out_row0 + (int)(b * kMatchQ);
+        blk.first_tile = (int)tiles.size();
+        for (long long s0 = 0; s0 < stages; s0 += per) {
+            MatchTile t{};
+            t.q_row0 = blk.q_row0;
+            t.q_rows = blk.q_rows;
+            t.t_set0 = (int)t0;
+            t.t_lo = (int)(s0 * kMatchT);
+            t.t_hi = (int)std::min<long long>(nt, (s0 + per) * kMatchT);
+            tiles.push_back(t);
+        }
+        blk.n_tiles = (int)tiles.size() - blk.first_tile;
+        blocks.push_back(blk);
+    }
+}
+
+int run(void* arg) {
+    const Job& j = *static_cast<const Job*>(arg);
+    MatchCtxView v = match_ctx_view(j.c);
+    SIFT_HIP_CHECK(hipSetDevice(v.device));
+
+    // ---- arguments ----
+    if (j.n_sets < 0 || j.n_pairs < 0 || (j.n_sets > 0 && !j.offsets) || (j.n_pairs > 0 && (!j.pair_q || !j.pair_t)))
+        return fail(j, "sift_hip match: bad set or pair arguments");
+    const long long rows = j.n_sets > 0 ? (long long)j.offsets[j.n_sets] : 0;
+    if (j.n_sets > 0 && j.offsets[0] < 0) return fail(j, "sift_hip match: offsets must start at >= 0");
+    for (int s = 0; s < j.n_sets; ++s)
+        if (j.offsets[s + 1] < j.offsets[s]) return fail(j, "sift_hip match: offsets must ascend");
+    if (rows > 0x7fffffffLL / 2) return fail(j, "sift_hip match: too many rows");
+    if (rows > 0 && !j.desc) return fail(j, "sift_hip match: no descriptors");
+    bool use_ratio = false, cross = false;
+    float ratio2 = 0.0f;
+    if (j.params) {
+        const float r = j.params->ratio;
+        if (!(r >= 0.0f && r <= 1.0f)) return fail(j, "sift_hip match: ratio must be 0 (no ratio test) or in (0, 1]");
+        use_ratio = r != 0.0f;
+        ratio2 = r * r;
+        cross = j.params->cross_check != 0;
+    }
+    long long fwd_rows = 0, rev_rows = 0;
+    for (int p = 0; p < j.n_pairs; ++p) {
+        const int q = j.pair_q[p], t = j.pair_t[p];
+        if (q < 0 || q >= j.n_sets || t < 0 || t >= j.n_sets) return fail(j, "sift_hip match: pair names a set that does not exist");
+        fwd_rows += j.offsets[q + 1] - j.offsets[q];
+        if (cross) rev_rows += j.offsets[t + 1] - j.offsets[t];
+    }
+    if (fwd_rows + rev_rows > 0x7fffffffLL / 2) return fail(j, "sift_hip match: too many query rows");
+    if (j.params ? (fwd_rows > 0 && !j.recs) : (fwd_rows > 0 && (!j.idx || !j.dist2))) return fail(j, "sift_hip match: no result array");
+
+    if (j.counts) std::fill(j.counts, j.counts + j.n_pairs, 0);
+    if (j.total) *j.total = 0;
+    if (fwd_rows == 0) return SIFT_HIP_OK;
+
+    if (!*v.state) *v.state = new MatchState();
+    MatchState& st = **v.state;
+
+    // ---- inputs on the device ----
+    const float* d_desc = j.desc;
+    const sift_hip_keypoint* d_kp = j.kp;
+    if (!j.inputs_on_device) {
+        if (!match_ptr_on_device(j.desc)) {
+            st.d_desc.ensure((size_t)rows * 128 * sizeof(float));
+            match_upload(j.c, st.d_desc.p, j.desc, (size_t)rows * 128 * sizeof(float));
+            match_wait(j.c);   // pageable memory travels through the context's two staging buffers: the next upload refills them
+            d_desc = st.d_desc.as<float>();
+        }
+        if (j.kp && !match_ptr_on_device(j.kp)) {
+            st.d_kp.ensure((size_t)rows * sizeof(sift_hip_keypoint));
+            match_upload(j.c, st.d_kp.p, j.kp, (size_t)rows * sizeof(sift_hip_keypoint));
+            d_kp = st.d_kp.as<sift_hip_keypoint>();
+        }
+    }
+
+    // ---- the tables: every pair's tiles (and, for the cross-check, those of the pair with its roles swapped) ----
+    long long q_blocks = 0;
+    for (int p = 0; p < j.n_pairs; ++p) {
+        const long long nq = j.offsets[j.pair_q[p] + 1] - j.offsets[j.pair_q[p]], nt = j.offsets[j.pair_t[p] + 1] - j.offsets[j.pair_t[p]];
+        q_blocks += (nq + kMatchQ - 1) / kMatchQ + (cross ? (nt + kMatchQ - 1) / kMatchQ : 0);
+    }
+    // one workgroup occupies a CU (LDS); with fewer than about four rounds of them the last round's idle CUs show, so below
+    // that the train sets are split further
+    const int want = 4 * resident_cus();
+    const int per_block = (int)std::max<long long>(1, (want + q_blocks - 1) / std::max<long long>(q_blocks, 1));
+    std::vector<MatchTile> tiles;
+    std::vector<MatchBlock> blocks;
+    std::vector<MatchPair> pairs((size_t)j.n_pairs);
+    long long out_row = 0, rev_row = fwd_rows;
+    for (int p = 0; p < j.n_pairs; ++p) {
+        const long long q0 = j.offsets[j.pair_q[p]], nq = j.offsets[j.pair_q[p] + 1] - q0;
+        const long long t0 = j.offsets[j.pair_t[p]], nt = j.offsets[j.pair_t[p] + 1] - t0;
+        pairs[(size_t)p] = MatchPair{(int)out_row, (int)nq, cross ? (int)rev_row : -1, 0};
+        add_tiles(q0, nq, t0, nt, per_block, (int)out_row, tiles, blocks);
+        out_row += nq;
+        if (cross) {
+            add_tiles(t0, nt, q0, nq, per_block, (int)rev_row, tiles, blocks);
+            rev_row += nt;
+        }
+    }
+    const long long all_rows = fwd_rows + rev_rows;
+
+    const size_t b_tiles = align256(tiles.size() * sizeof(MatchTile)), b_blocks = align256(blocks.size() * sizeof(MatchBlock)),
+                 b_pairs = align256(pairs.size() * sizeof(MatchPair));
+    if (b_tiles + b_blocks + b_pairs > st.h_cap) {
+        ApiGuard api;
+        if (st.h_tables) SIFT_HIP_CHECK(hipHostFree(st.h_tables));
+        st.h_tables = nullptr;
+        st.h_cap = 0;
+        SIFT_HIP_CHECK(hipHostMalloc(&st.h_tables, 2 * (b_tiles + b_blocks + b_pairs), hipHostMallocDefault));
+        st.h_cap = 2 * (b_tiles + b_blocks + b_pairs);
+    }
+    char* h = static_cast<char*>(st.h_tables);
+    std::memcpy(h, tiles.data(), tiles.size() * sizeof(MatchTile));
+    std::memcpy(h + b_tiles, blocks.data(), blocks.size() * sizeof(MatchBlock));
+    std::memcpy(h + b_tiles + b_blocks, pairs.data(), pairs.size() * sizeof(MatchPair));
+    st.d_tiles.ensure(b_tiles);
+    st.d_blocks.ensure(b_blocks);
+    st.d_pairs.ensure(b_pairs);
+    if (!tiles.empty()) SIFT_HIP_CHECK(hipMemcpyAsync(st.d_tiles.p, h, b_tiles, hipMemcpyHostToDevice, v.stream));
+    SIFT_HIP_CHECK(hipMemcpyAsync(st.d_blocks.p, h + b_tiles, b_blocks, hipMemcpyHostToDevice, v.stream));
+    SIFT_HIP_CHECK(hipMemcpyAsync(st.d_pairs.p, h + b_tiles + b_blocks, b_pairs, hipMemcpyHostToDevice, v.stream));
+
+    st.d_norm.ensure((size_t)rows * sizeof(float));
+    st.d_valid.ensure((size_t)rows);
+    st.d_part.ensure(std::max<size_t>(tiles.size(), 1) * kMatchQ * sizeof(MatchTop2));
+    const bool idx_direct = !j.params && match_ptr_on_device(j.idx), dist_direct = !j.params && match_ptr_on_device(j.dist2);
+    if (!idx_direct) st.d_idx.ensure((size_t)all_rows * 2 * sizeof(int32_t));
+    if (!dist_direct) st.d_dist.ensure((size_t)all_rows * 2 * sizeof(float));
+    int32_t* d_idx = idx_direct ? j.idx : st.d_idx.as<int32_t>();
+    float* d_dist = dist_direct ? j.dist2 : st.d_dist.as<float>();
+
+    // ---- the launches: one of each kernel, whatever the number of pairs ----
+    launch_match_norms(v.stream, d_desc, d_kp, rows, st.d_norm.as<float>(), st.d_valid.as<uint8_t>());
+    launch_match_tiles(v.stream, d_desc, st.d_norm.as<float>(), st.d_valid.as<uint8_t>(), st.d_tiles.as<MatchTile>(), (int)tiles.size(),
+                       st.d_part.as<MatchTop2>());
+    launch_match_merge(v.stream, st.d_part.as<MatchTop2>(), st.d_valid.as<uint8_t>(), st.d_blocks.as<MatchBlock>(), (int)blocks.size(), d_idx,
+                       d_dist);
+    SIFT_HIP_CHECK(hipGetLastError());
+
+    if (!j.params) {
+        if (!idx_direct) match_download(j.c, j.idx, d_idx, (size_t)fwd_rows * 2 * sizeof(int32_t));
+        if (!dist_direct) match_download(j.c, j.dist2, d_dist, (size_t)fwd_rows * 2 * sizeof(float));
+        match_wait(j.c);
+        return SIFT_HIP_OK;
+    }
+
+    const bool recs_direct = match_ptr_on_device(j.recs);
+    st.d_seg.ensure((size_t)fwd_rows * sizeof(sift_hip_match_rec));
+    st.d_counts.ensure((size_t)j.n_pairs * sizeof(int32_t));
+    if (!recs_direct) st.d_out.ensure((size_t)fwd_rows * sizeof(sift_hip_match_rec));
+    sift_hip_match_rec* d_out = recs_direct ? j.recs : st.d_out.as<sift_hip_match_rec>();
+    launch_match_filter(v.stream, d_idx, d_dist, st.d_pairs.as<MatchPair>(), j.n_pairs, use_ratio ? 1 : 0, ratio2, cross ? 1 : 0,
+                        st.d_seg.as<sift_hip_match_rec>(), st.d_counts.as<int32_t>());
+    launch_match_pack(v.stream, st.d_seg.as<sift_hip_match_rec>(), st.d_pairs.as<MatchPair>(), st.d_counts.as<int32_t>(), j.n_pairs, d_out);
+    SIFT_HIP_CHECK(hipGetLastError());
+    st.counts.assign((size_t)j.n_pairs, 0);
+    match_download(j.c, st.counts.data(), st.d_counts.p, (size_t)j.n_pairs * sizeof(int32_t));
+    long long total = 0;
+    for (int32_t n : st.counts) total += n;
+    if (!recs_direct && total > 0) match_download(j.c, j.recs, d_out, (size_t)total * sizeof(sift_hip_match_rec));
+    match_wait(j.c);
+    if (j.counts) std::copy(st.counts.begin(), st.counts.end(), j.counts);
+    if (j.total) *j.total = total;
+    return SIFT_HIP_OK;
+}
+
+}  // namespace
+}  // namespace sift_hip
+
+using namespace sift_hip;
+
+extern "C" {
+
+int sift_hip_knn2(sift_hip_ctx* c, const float* desc, const sift_hip_keypoint* kp, int n_sets, const int64_t* offsets, int n_pairs,
+                  const int32_t* pair_q, const int32_t* pair_t, int32_t* idx, float* dist2, char* err, int errlen) {
+    if (!c) { match_set_err(err, errlen, "sift_hip_knn2: no context (matching runs on the GPU only)"); return SIFT_HIP_EINVAL; }
+    Job j{c, desc, kp, false, n_sets, offsets, n_pairs, pair_q, pair_t, nullptr, idx, dist2, nullptr, nullptr, nullptr, err, errlen};
+    return match_guarded(err, errlen, run, &j);
+}
+
+int sift_hip_match(sift_hip_ctx* c, const float* desc, const sift_hip_keypoint* kp, int n_sets, const int64_t* offsets, int n_pairs,
+                   const int32_t* pair_q, const int32_t* pair_t, const sift_hip_match_params* params, sift_hip_match_rec* recs,
+                   int32_t* counts, int64_t* total, char* err, int errlen) {
+    if (!c) { match_set_err(err, errlen, "sift_hip_match: no context (matching runs on the GPU only)"); return SIFT_HIP_EINVAL; }
+    if (!params) { match_set_err(err, errlen, "sift_hip_match: no parameters"); return SIFT_HIP_EINVAL; }
+    Job j{c, desc, kp, false, n_sets, offsets, n_pairs, pair_q, pair_t, params, nullptr, nullptr, recs, counts, total, err, errlen};
+    return match_guarded(err, errlen, run, &j);
+}
+
+int sift_hip_result_match(sift_hip_ctx* c, int n_pairs, const int32_t* pair_q, const int32_t* pair_t, const sift_hip_match_params* params,
+                          sift_hip_match_rec* recs, int32_t* counts, int64_t* total, char* err, int errlen) {
+    if (!c) { match_set_err(err, errlen, "sift_hip_result_match: no context (matching runs on the GPU only)"); return SIFT_HIP_EINVAL; }
+    if (!params) { match_set_err(err, errlen, "sift_hip_result_match: no parameters"); return SIFT_HIP_EINVAL; }
+    const MatchCtxView v = match_ctx_view(c);
+    if (!v.have_result) { match_set_err(err, errlen, "sift_hip_result_match: the context holds no results"); return SIFT_HIP_EINVAL; }
+    std::vector<int64_t> offsets((size_t)v.n_images + 1, 0);
+    for (int i = 0; i < v.n_images; ++i) offsets[(size_t)i + 1] = offsets[(size_t)i] + v.counts[i];
+    Job j{c, v.d_desc, v.d_kp, true, v.n_images, offsets.data(), n_pairs, pair_q, pair_t, params, nullptr, nullptr, recs, counts, total, err, errlen};
+    return match_guarded(err, errlen, run, &j);
+}
+
+}  // extern "C"

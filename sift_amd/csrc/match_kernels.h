@@ -1,0 +1,71 @@
+// Descriptor matching: the records the host (match.cpp) hands to the kernels (kernels_match.hip), their launchers, and what
+// match.cpp needs from a context (accessors defined in context.cpp).  The definition of the result is in include/sift_hip.h.
+#pragma once
+#include <stdint.h>
+
+#include "common.h"
+
+namespace sift_hip {
+
+constexpr int kMatchQ = 128;          // query rows a workgroup of the tile kernel keeps in LDS
+constexpr int kMatchT = 64;           // train rows per LDS stage
+constexpr int kMatchSplitRows = 256;  // a split of a train set is a multiple of this many rows (host-side choice, never visible)
+constexpr int kMatchNone = 0x7fffffff;   // index of a missing entry inside the kernels (sorts after every row); -1 on the way out
+
+// one workgroup of the tile kernel: a block of query rows against a range of its train set
+struct MatchTile {
+    int q_row0, q_rows;   // first query row (row of the descriptor array), rows of the block (<= kMatchQ)
+    int t_set0;           // first row of the train set
+    int t_lo, t_hi;       // train rows [t_lo, t_hi) of the set, t_lo a multiple of kMatchT
+    int pad;
+};
+// one block of query rows of one pair: its partial top-2s (tiles first_tile .. + n_tiles) become rows of the result
+struct MatchBlock {
+    int q_row0, q_rows;
+    int out_row0;         // row of the idx / dist2 arrays
+    int first_tile, n_tiles;
+    int pad;
+};
+struct MatchTop2 { float d1, d2; int i1, i2; };   // partial result of one query row in one tile
+static_assert(sizeof(sift_hip_match_rec) == 16 && sizeof(sift_hip_match_params) == 8 && sizeof(MatchTop2) == 16, "match record packing");
+// one pair of the filter: its rows of the top-2 arrays, the rows of the reverse best (cross-check; -1 none)
+struct MatchPair {
+    int row0, rows;
+    int rev_row0;
+    int pad;
+};
+
+void launch_match_norms(hipStream_t s, const float* d_desc, const sift_hip_keypoint* d_kp, long long rows, float* d_norm, uint8_t* d_valid);
+void launch_match_tiles(hipStream_t s, const float* d_desc, const float* d_norm, const uint8_t* d_valid, const MatchTile* d_tiles,
+                        int n_tiles, MatchTop2* d_part);
+void launch_match_merge(hipStream_t s, const MatchTop2* d_part, const uint8_t* d_valid, const MatchBlock* d_blocks, int n_blocks,
+                        int32_t* d_idx, float* d_dist);
+// records of every pair at the pair's own rows of d_seg (query order), per-pair counts; then the dense list in pair order
+void launch_match_filter(hipStream_t s, const int32_t* d_idx, const float* d_dist, const MatchPair* d_pairs, int n_pairs, int use_ratio,
+                         float ratio2, int cross_check, sift_hip_match_rec* d_seg, int32_t* d_counts);
+void launch_match_pack(hipStream_t s, const sift_hip_match_rec* d_seg, const MatchPair* d_pairs, const int32_t* d_counts, int n_pairs,
+                       sift_hip_match_rec* d_out);
+void tu_touch_match(hipStream_t s);
+
+// ---- the context as match.cpp sees it (context.cpp) ---------------------------------------------------------
+struct MatchState;                       // scratch of the matcher, owned by the context once the first match call made it
+void match_state_free(MatchState* st);   // match.cpp; sift_hip_destroy calls it
+struct MatchCtxView {
+    int device;
+    hipStream_t stream;
+    bool have_result;
+    const sift_hip_keypoint* d_kp;       // results of the last batch (sift_hip_result_device)
+    const float* d_desc;
+    const int32_t* counts;
+    int n_images;
+    MatchState** state;
+};
+MatchCtxView match_ctx_view(sift_hip_ctx* c);
+bool match_ptr_on_device(const void* p);                                              // as sift_hip_result_copy tells its targets apart
+void match_upload(sift_hip_ctx* c, void* dev, const void* host, size_t bytes);        // queued on the context's stream
+void match_download(sift_hip_ctx* c, void* dst, const void* dev, size_t bytes);       // complete on return
+void match_wait(sift_hip_ctx* c);
+int match_guarded(char* err, int errlen, int (*fn)(void*), void* arg);                // HIP failures -> SIFT_HIP_EHIP + text
+void match_set_err(char* err, int errlen, const char* msg);
+
+}  // namespace sift_hip

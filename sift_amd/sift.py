@@ -346,6 +346,105 @@ class Context:
     def profile_reset(self):
         self._L.sift_hip_profile_reset(self._h)
 
+    # ---- descriptor matching (include/sift_hip.h, "descriptor matching") --------------------------------
+    @staticmethod
+    def _addr(a):
+        """Address of a numpy array, of a tensor (data_ptr) or a plain integer address: host or device memory."""
+        if a is None:
+            return None
+        if isinstance(a, np.ndarray):
+            return C.c_void_p(a.ctypes.data)
+        if hasattr(a, "data_ptr"):
+            return C.c_void_p(a.data_ptr())
+        return C.c_void_p(int(a))
+
+    @staticmethod
+    def _pairs(pairs):
+        p = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+        return np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(p[:, 1])
+
+    def knn2_sets(self, desc, offsets, pairs, kp=None, idx_out=None, dist_out=None):
+        """sift_hip_knn2: top-2 of every query row of every pair -> (idx [rows, 2] int32, dist2 [rows, 2] float32), rows = the
+        pairs' query rows in pair order.  `desc` / `kp`: numpy arrays, tensors or addresses (host or device memory); `idx_out` /
+        `dist_out`: where the result goes instead of new numpy arrays (returned as given)."""
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        pq, pt = self._pairs(pairs)
+        rows = int(sum(offsets[q + 1] - offsets[q] for q in pq if 0 <= q < offsets.size - 1))
+        idx = np.full((rows, 2), -1, np.int32) if idx_out is None else idx_out
+        dist = np.full((rows, 2), np.inf, np.float32) if dist_out is None else dist_out
+        if isinstance(desc, np.ndarray):
+            desc = np.ascontiguousarray(desc, np.float32)
+        err = C.create_string_buffer(512)
+        rc = self._L.sift_hip_knn2(self._h, self._addr(desc), self._addr(kp), offsets.size - 1, offsets, pq.size, pq, pt,
+                                   self._addr(idx), self._addr(dist), err, 512)
+        if rc:
+            _raise(rc, err)
+        return idx, dist
+
+    def knn2(self, q, t, q_kp=None, t_kp=None):
+        """Top-2 train rows of every row of `q` [nq, 128] among `t` [nt, 128] (numpy, host memory).  `q_kp` / `t_kp`: keypoint
+        records whose has_descriptor decides which rows are valid (None: all)."""
+        q = np.ascontiguousarray(q, np.float32).reshape(-1, 128)
+        t = np.ascontiguousarray(t, np.float32).reshape(-1, 128)
+        desc, offsets, kp = self._two_sets(q, t, q_kp, t_kp)
+        return self.knn2_sets(desc, offsets, [(0, 1)], kp)
+
+    @staticmethod
+    def _two_sets(q, t, q_kp, t_kp):
+        desc = np.concatenate([q, t])
+        offsets = np.array([0, q.shape[0], q.shape[0] + t.shape[0]], np.int64)
+        kp = None
+        if q_kp is not None or t_kp is not None:
+            kp = np.zeros(desc.shape[0], _lib.KEYPOINT_DTYPE)
+            kp["has_descriptor"] = 1
+            if q_kp is not None:
+                kp[:q.shape[0]] = q_kp
+            if t_kp is not None:
+                kp[q.shape[0]:] = t_kp
+        return desc, offsets, kp
+
+    def match_sets(self, desc, offsets, pairs, ratio=0.8, cross_check=False, kp=None, recs_out=None):
+        """sift_hip_match: the filtered matches of every pair -> (records, counts): records (query, train, dist2, second2) in
+        pair order, then query order; counts[p] of them belong to pair p.  `recs_out`: a tensor / address with room for one
+        record per query row (then the first element returned is the total instead of an array)."""
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        pq, pt = self._pairs(pairs)
+        rows = int(sum(offsets[q + 1] - offsets[q] for q in pq if 0 <= q < offsets.size - 1))
+        recs = np.zeros(rows, _lib.MATCH_DTYPE) if recs_out is None else recs_out
+        counts = np.zeros(pq.size, np.int32)
+        total = C.c_int64()
+        if isinstance(desc, np.ndarray):
+            desc = np.ascontiguousarray(desc, np.float32)
+        prm = _lib.MatchParams(float(ratio), 1 if cross_check else 0)
+        err = C.create_string_buffer(512)
+        rc = self._L.sift_hip_match(self._h, self._addr(desc), self._addr(kp), offsets.size - 1, offsets, pq.size, pq, pt, C.byref(prm),
+                                    self._addr(recs), counts, C.byref(total), err, 512)
+        if rc:
+            _raise(rc, err)
+        return (recs[:total.value] if recs_out is None else int(total.value)), counts
+
+    def match(self, q, t, ratio=0.8, cross_check=False, q_kp=None, t_kp=None):
+        """Matches of the rows of `q` among `t` (numpy, host memory): records (query, train, dist2, second2) in query order."""
+        q = np.ascontiguousarray(q, np.float32).reshape(-1, 128)
+        t = np.ascontiguousarray(t, np.float32).reshape(-1, 128)
+        desc, offsets, kp = self._two_sets(q, t, q_kp, t_kp)
+        return self.match_sets(desc, offsets, [(0, 1)], ratio, cross_check, kp)[0]
+
+    def match_images(self, pairs, ratio=0.8, cross_check=False):
+        """sift_hip_result_match: matches between images of the last batch, on the device-resident results -> (records, counts)."""
+        pq, pt = self._pairs(pairs)
+        cnt = self.counts() if self._L.sift_hip_result_images(self._h) >= 0 else np.zeros(0, np.int32)   # none: the call says so
+        rows = int(sum(cnt[q] for q in pq if 0 <= q < cnt.size))
+        recs = np.zeros(rows, _lib.MATCH_DTYPE)
+        counts = np.zeros(pq.size, np.int32)
+        total = C.c_int64()
+        prm = _lib.MatchParams(float(ratio), 1 if cross_check else 0)
+        err = C.create_string_buffer(512)
+        rc = self._L.sift_hip_result_match(self._h, pq.size, pq, pt, C.byref(prm), C.c_void_p(recs.ctypes.data), counts, C.byref(total), err, 512)
+        if rc:
+            _raise(rc, err)
+        return recs[:total.value], counts
+
 
 class Group:
     """sift_hip_group: one batch block-sharded over several GPUs of this node from one process (one context and host thread
@@ -514,3 +613,18 @@ class Sift:
         self.ctx.calculate_batch(imgs, self._params)
         kp, desc = self.ctx.results()
         return self.ctx.counts(), kp, desc
+
+    def match(self, points_a, points_b, ratio: float = 0.8, cross_check: bool = False):
+        """Matches between two InterestPoint lists (an extension: the reference has no matcher) -> records (query, train,
+        dist2, second2), indices into the lists.  A point without a 128-float descriptor is an invalid row."""
+        def rows(points):
+            d = np.zeros((len(points), 128), np.float32)
+            kp = np.zeros(len(points), _lib.KEYPOINT_DTYPE)
+            for i, p in enumerate(points):
+                if len(p.descriptors) == 128:
+                    d[i] = p.descriptors
+                    kp["has_descriptor"][i] = 1
+            return d, kp
+        qa, ka = rows(points_a)
+        qb, kb = rows(points_b)
+        return self.ctx.match(qa, qb, ratio, cross_check, ka, kb)
