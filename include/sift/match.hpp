@@ -18,6 +18,13 @@ struct Match {
     f32_t dist2 = 0.0f, second2 = 0.0f;  // squared distance to the best and to the second best train point (+inf: none)
 };
 
+struct Homography {
+    f32_t h[9] = {};                     // row-major, query image -> train image: (tx, ty, 1) ~ H (qx, qy, 1); the best minimal-sample model
+    int inliers = 0;
+    int iteration = -1;                  // the winning hypothesis; -1: no model (fewer than four matches, or every sample degenerate)
+    std::vector<unsigned char> inlier;   // one flag per match handed to Matcher::verify
+};
+
 class Matcher {
 public:
     explicit Matcher(int device = 0) {
@@ -65,11 +72,46 @@ public:
         return out;
     }
 
+    // The geometric check of a match list (include/sift_hip.h, "geometric verification"): the best four-point homography
+    // from the query image to the train image over the matches' image coordinates, loc * 2^octave (halved when the points
+    // come from a subpixel run), and one flag per match.  Throws std::invalid_argument for iterations outside 1 .. 65536 or a
+    // threshold that is not finite and positive.
+    Homography verify(const std::vector<InterestPoint>& query, const std::vector<InterestPoint>& train, const std::vector<Match>& matches,
+                      unsigned iterations = 2048, f32_t threshold = 3.0f, unsigned seed = 0, bool subpixel = false) {
+        const f32_t scale = subpixel ? 0.5f : 1.0f;
+        _pts.resize(matches.size() * 4);
+        for (size_t i = 0; i < matches.size(); ++i) {
+            const InterestPoint& q = query.at((size_t)matches[i].query);
+            const InterestPoint& t = train.at((size_t)matches[i].train);
+            _pts[4 * i] = (f32_t)((unsigned)q.loc.x << q.octave) * scale;
+            _pts[4 * i + 1] = (f32_t)((unsigned)q.loc.y << q.octave) * scale;
+            _pts[4 * i + 2] = (f32_t)((unsigned)t.loc.x << t.octave) * scale;
+            _pts[4 * i + 3] = (f32_t)((unsigned)t.loc.y << t.octave) * scale;
+        }
+        const int64_t offsets[2] = {0, (int64_t)matches.size()};
+        sift_hip_ransac_params prm{};
+        prm.iterations = iterations;
+        prm.seed = seed;
+        prm.threshold = threshold;
+        sift_hip_homography model{};
+        Homography out;
+        out.inlier.assign(matches.size(), 0);
+        char err[512] = "";
+        const int rc = sift_hip_ransac_homography(_ctx, _pts.data(), 1, offsets, &prm, &model, out.inlier.data(), nullptr, err, sizeof(err));
+        if (rc == SIFT_HIP_EINVAL) throw std::invalid_argument(err);
+        if (rc != SIFT_HIP_OK) throw std::runtime_error(err);
+        for (int k = 0; k < 9; ++k) out.h[k] = model.h[k];
+        out.inliers = model.inliers;
+        out.iteration = model.iteration;
+        return out;
+    }
+
 private:
     sift_hip_ctx* _ctx = nullptr;
     std::vector<float> _desc;              // both lists' rows back to back, kept between calls
     std::vector<sift_hip_keypoint> _kp;
     std::vector<sift_hip_match_rec> _recs;
+    std::vector<float> _pts;
 };
 
 }  // namespace sift

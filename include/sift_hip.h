@@ -232,6 +232,60 @@ int sift_hip_result_match(sift_hip_ctx* ctx, int n_pairs, const int32_t* pair_q,
                           const sift_hip_match_params* params, sift_hip_match_rec* recs, int32_t* counts, int64_t* total,
                           char* err, int errlen);
 
+/* ---- geometric verification: RANSAC homography over match lists (an extension) ---------------------------
+ * A correspondence is a row of four floats (qx, qy, tx, ty); the model maps query to train: (tx, ty, 1) ~ H (qx, qy, 1), H
+ * row-major.  The result is defined bit for bit by sift_amd/csrc/ransac_math.h, which the kernels and a plain host loop
+ * (hostmath_ransac_homography) both compile.  In words, for a set of m rows and hypothesis i = 0 .. iterations - 1:
+ *   sample     four distinct rows from a counter-based integer hash of (seed, set number, i): draw k is
+ *              (uint64(hash) * (m - k)) >> 32, stepped over the rows already drawn; no state between hypotheses, so hypothesis
+ *              i of set s depends on (seed, s, i, m) and the points only.  The set number is the position in THIS call.
+ *   solve      in double, branch-free: for each side the projective basis [l0 p0, l1 p1, l2 p2], l = adj([p0 p1 p2]) p3;
+ *              H = B adj(A), A the query side's and B the train side's basis.  Invalid when one of the eight determinants
+ *              (l0 .. l2 and det [p0 p1 p2] of both sides) is zero or not finite (collinear or coincident sample points, NaN
+ *              or infinite coordinates), when the four products of corresponding determinants do not share one strict sign
+ *              (the orientation test: W would change sign inside the sample), or when an entry of H is not finite.  A valid H is
+ *              divided by its entry of largest magnitude (the first one), negated if W of the first sample row is negative,
+ *              and rounded to nine floats.
+ *   predicate  in float, no division: X = fmaf(h0, qx, fmaf(h1, qy, h2)), Y and W likewise; ex = fmaf(-tx, W, X), ey = fmaf(-ty,
+ *              W, Y), e2 = fmaf(ex, ex, ey * ey); inlier iff W > 0 and e2 <= (thr * thr) * (W * W) and e2 < +inf.  A NaN or an
+ *              infinity anywhere in a row makes it no inlier of any model.
+ *   selection  score = inliers among ALL m rows, or -1 for an invalid hypothesis; the winner has the highest score, the lowest i
+ *              among equals.  No valid hypothesis, or m < 4: iteration -1, inliers 0, h all +0.0f, every flag 0.
+ * Scores are integers, so the result does not depend on how rows or hypotheses are tiled, split over workgroups or reduced.
+ * The returned H is the best MINIMAL-SAMPLE model: there is no least-squares refit over the inliers (a follow-up: its sums
+ * would need a fixed order), no adaptive early stop and no other model. */
+typedef struct sift_hip_ransac_params {
+    uint32_t iterations;  /* hypotheses per set, 1 .. 65536 */
+    uint32_t seed;
+    float threshold;      /* pixels, finite and > 0 */
+    uint32_t reserved;
+} sift_hip_ransac_params;
+typedef struct sift_hip_homography {
+    float h[9];           /* row-major */
+    int32_t inliers;      /* score of the winner = number of flags set */
+    int32_t iteration;    /* the winning hypothesis; -1: none */
+    int32_t reserved;
+} sift_hip_homography;
+/* pts: the sets' rows back to back (host memory, or device memory aligned to 16 bytes); offsets as for the match calls
+ * (n_sets + 1 entries, host memory).  models: n_sets records; inlier (may be NULL): one byte per row, 1 = inlier of its set's winner; scores (may be
+ * NULL): n_sets x iterations int32, the score of every hypothesis.  The three may each be host or device memory.  Empty sets
+ * are legal.  All sets of a call share one launch of each kernel.  SIFT_HIP_EINVAL for iterations 0 or above 65536, a
+ * threshold that is not finite and positive, or bad offsets.  Runs on the context's stream, returns when the results are in
+ * place; scratch memory is allocated by the first call and kept with the context. */
+int sift_hip_ransac_homography(sift_hip_ctx* ctx, const float* pts, int n_sets, const int64_t* offsets,
+                               const sift_hip_ransac_params* params, sift_hip_homography* models, uint8_t* inlier,
+                               int32_t* scores, char* err, int errlen);
+/* sift_hip_result_match followed by the verification of its lists, on the device-resident results: pair p is set p, row i of
+ * the set is record i of the pair, with qx = (float)(x << octave) of the record's query keypoint (qy, tx, ty likewise), times
+ * 0.5f when the last batch ran with subpixel (both exact in float) - built on the GPU.  recs, counts, total as
+ * sift_hip_result_match delivers them; models: n_pairs records; inlier (may be NULL): one byte per record of `recs`.  Bit for
+ * bit the result of sift_hip_result_match plus sift_hip_ransac_homography on those coordinates; only records, flags and
+ * models leave the GPU.  recs, models and inlier may each be host or device memory. */
+int sift_hip_result_verify(sift_hip_ctx* ctx, int n_pairs, const int32_t* pair_q, const int32_t* pair_t,
+                           const sift_hip_match_params* match_params, const sift_hip_ransac_params* ransac_params,
+                           sift_hip_match_rec* recs, int32_t* counts, int64_t* total, sift_hip_homography* models,
+                           uint8_t* inlier, char* err, int errlen);
+
 /* ---- inspection of the last batch (parity tests) ------------------------------------------------ */
 /* kind: 0 gaussian (levels 0..D), 1 dog (0..D-1), 2 magnitude, 3 orientation (initial gradient
  * maps, sift.cpp:130-160, only for levels some keypoint scale selects; 0x0 otherwise). */

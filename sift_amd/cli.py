@@ -3,6 +3,7 @@ overlay :59-76) on top of the GPU path — SURVEY.md §8(f) rows 1-3.
 
     python -m sift_amd.cli -i image.pgm [-s 1.6] [-k 1.41421354] [-o 4] [-d 3] [-p 0] [-r 1]
     python -m sift_amd.cli -i a.pgm --match b.pgm [--ratio 0.8] [--cross-check]      (an extension: matches.txt)
+    python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--iterations 2048] [--threshold 3] [--seed 0]   (... and inliers.txt)
 
 Image ingest follows Vigra's scalar import: band 0 of multi-band files, values unscaled.  PGM,
 PPM, PNG and JPEG are decoded by the library itself (sift_amd/csrc/image_io.cpp, jpeg_decode.cpp: no PIL, no OpenCV, no libjpeg).
@@ -131,7 +132,13 @@ def main(argv=None) -> int:
     ap.add_argument("--match", metavar="IMG2", help="also run IMG2 and write the matches of the image's points among IMG2's to matches.txt")
     ap.add_argument("--ratio", type=float, default=0.8, help="ratio test of --match (0: none)")
     ap.add_argument("--cross-check", action="store_true", help="--match keeps mutual best matches only")
+    ap.add_argument("--verify", action="store_true", help="with --match: a RANSAC homography over the matches; its inliers go to inliers.txt")
+    ap.add_argument("--iterations", type=int, default=2048, help="hypotheses of --verify (1 .. 65536)")
+    ap.add_argument("--threshold", type=float, default=3.0, help="inlier threshold of --verify in pixels")
+    ap.add_argument("--seed", type=int, default=0, help="seed of --verify's sampling")
     args = ap.parse_args(argv)
+    if args.verify and not args.match:
+        ap.error("--verify needs --match")
     path = args.img or args.img_pos
     if not path:
         ap.print_help()
@@ -147,9 +154,20 @@ def main(argv=None) -> int:
         print(f"{len(points)} interest points")
         if args.match:
             points2 = sift.calculate(_load(args.match))
-            matches = sift.match(points, points2, args.ratio, args.cross_check)
+            if not args.verify:
+                matches = sift.match(points, points2, args.ratio, args.cross_check)
+            else:
+                matches, model, inlier = sift.verify(points, points2, args.ratio, args.cross_check, args.iterations, args.threshold, args.seed)
             write_matches("matches.txt", matches)
             print(f"{len(points2)} interest points in {args.match}, {len(matches)} matches")
+            if args.verify:
+                write_matches("inliers.txt", matches[inlier != 0])
+                print(f"{int(model['inliers'])} inliers -> inliers.txt")
+                if model["iteration"] < 0:
+                    print("no homography")
+                else:
+                    for r in range(3):
+                        print("H " + " ".join("%.9g" % float(v) for v in model["h"][3 * r:3 * r + 3]))
     except (PreconditionViolation, AssertionError, RuntimeError, OSError) as ex:  # main.cpp:90-92
         print(ex, file=sys.stderr)
     return 0

@@ -20,6 +20,7 @@
 #include "phase_gate.h"
 #include "host_glue.h"
 #include "match_kernels.h"
+#include "ransac_kernels.h"
 
 using namespace sift_hip;
 
@@ -206,6 +207,7 @@ struct sift_hip_ctx {
     double prof_busy_ms[kProfClasses] = {0, 0, 0, 0, 0};   // time during which at least one launch of the class was running (union of the launches' intervals)
     long long prof_batches = 0;           // batches whose launches carried the events since the last reset
     sift_hip::MatchState* match_state = nullptr;   // the matcher's scratch (match.cpp), made by the first match call
+    sift_hip::RansacState* ransac_state = nullptr; // the same for the geometric verification (ransac.cpp)
 };
 
 namespace {
@@ -1290,6 +1292,8 @@ void match_download(sift_hip_ctx* c, void* dst, const void* dev, size_t bytes) {
 void match_wait(sift_hip_ctx* c) { wait_stream(c, c->stream); }
 int match_guarded(char* err, int errlen, int (*fn)(void*), void* arg) { return guarded(err, errlen, [&]() { return fn(arg); }); }
 void match_set_err(char* err, int errlen, const char* msg) { set_err(err, errlen, msg); }
+RansacState** ransac_ctx_state(sift_hip_ctx* c) { return &c->ransac_state; }
+bool ransac_ctx_subpixel(sift_hip_ctx* c) { return c->plan.params.subpixel != 0; }
 }  // namespace sift_hip
 
 // =====================================================================================================
@@ -1354,6 +1358,7 @@ void sift_hip_destroy(sift_hip_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     (void)sift_hip_set_gate(c, nullptr);
     match_state_free(c->match_state);
+    ransac_state_free(c->ransac_state);
     ApiGuard api;
     for (DevBuf* b : {&c->arena, &c->d_plan, &c->d_taps, &c->d_luts, &c->d_taps16, &c->d_input, &c->d_input_u8, &c->d_sparse_rec, &c->d_sparse_val, &c->d_base, &c->d_tmp, &c->d_tmp2,
                       &c->d_wk, &c->d_wi, &c->d_wi2, &c->d_wp, &c->d_status, &c->d_pool, &c->d_order, &c->d_masks, &c->d_fmasks, &c->d_counts, &c->d_tile_counts, &c->d_totals, &c->d_cands, &c->d_flags, &c->d_list, &c->d_list_cnt, &c->d_orient,

@@ -8,6 +8,8 @@
 #include "grad_math.h"
 #include "hist_bins.h"
 #include "linalg3.h"
+#include "ransac_math.h"
+#include "../../include/sift_hip.h"   // sift_hip_homography
 
 extern "C" {
 float hostmath_atan2f(float y, float x) { return sift_hip::fdlibm_atan2f(y, x); }
@@ -107,5 +109,65 @@ void hostmath_match_knn2(const float* q, const uint8_t* q_valid, long long nq, c
         dist2[2 * i] = d1; dist2[2 * i + 1] = d2;
     }
     delete[] tn;
+}
+// RANSAC homography as ransac_math.h defines it, in plain loops: what sift_hip_ransac_homography must reproduce bit for bit.
+void hostmath_ransac_draw(uint32_t seed, uint32_t set, uint32_t iteration, uint32_t m, uint32_t* idx) {
+    uint32_t d[4];
+    sift_hip::ransac_draw(seed, set, iteration, m, d);
+    for (int k = 0; k < 4; ++k) idx[k] = d[k];
+}
+// c: four rows (qx, qy, tx, ty); h: nine floats; returns 1 when the sample gives a model
+int hostmath_homography4(const float* c, float* h) {
+    float cc[4][4], hh[9];
+    for (int k = 0; k < 16; ++k) cc[k / 4][k % 4] = c[k];
+    const bool ok = sift_hip::ransac_homography4(cc, hh);
+    for (int k = 0; k < 9; ++k) h[k] = hh[k];
+    return ok ? 1 : 0;
+}
+int hostmath_ransac_inlier(const float* h, const float* row, float thr) {
+    float hh[9];
+    for (int k = 0; k < 9; ++k) hh[k] = h[k];
+    return sift_hip::ransac_inlier(hh, row[0], row[1], row[2], row[3], thr * thr) ? 1 : 0;
+}
+// pts: rows of four floats, set s = rows offsets[s] .. offsets[s+1] - 1; inlier (one byte per row) and scores (n_sets x
+// iterations) may be NULL
+void hostmath_ransac_homography(const float* pts, int n_sets, const int64_t* offsets, uint32_t iterations, uint32_t seed, float thr,
+                                sift_hip_homography* models, uint8_t* inlier, int32_t* scores) {
+    const float thr2 = thr * thr;
+    if (inlier && n_sets > 0)
+        for (int64_t i = 0; i < offsets[0]; ++i) inlier[i] = 0;   // rows in front of the first set belong to none
+    for (int s = 0; s < n_sets; ++s) {
+        const float* p = pts + 4 * offsets[s];
+        const int64_t m = offsets[s + 1] - offsets[s];
+        sift_hip_homography best{};
+        best.iteration = -1;
+        int32_t best_score = -1;
+        for (uint32_t it = 0; it < iterations; ++it) {
+            int32_t score = -1;
+            float h[9] = {};
+            if (m >= 4) {
+                uint32_t d[4];
+                float c[4][4];
+                sift_hip::ransac_draw(seed, (uint32_t)s, it, (uint32_t)m, d);
+                for (int k = 0; k < 4; ++k)
+                    for (int e = 0; e < 4; ++e) c[k][e] = p[4 * (int64_t)d[k] + e];
+                if (sift_hip::ransac_homography4(c, h)) {
+                    score = 0;
+                    for (int64_t i = 0; i < m; ++i) score += sift_hip::ransac_inlier(h, p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], thr2) ? 1 : 0;
+                }
+            }
+            if (scores) scores[(int64_t)s * iterations + it] = score;
+            if (score > best_score) {   // strictly: the lowest iteration keeps a tie
+                best_score = score;
+                for (int k = 0; k < 9; ++k) best.h[k] = h[k];
+                best.inliers = score;
+                best.iteration = (int32_t)it;
+            }
+        }
+        models[s] = best;
+        if (inlier)
+            for (int64_t i = 0; i < m; ++i)
+                inlier[offsets[s] + i] = best.iteration >= 0 && sift_hip::ransac_inlier(best.h, p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], thr2) ? 1 : 0;
+    }
 }
 }

@@ -1,0 +1,170 @@
+// RANSAC homography over match lists (include/sift_hip.h, "geometric verification").  The arithmetic is ransac_math.h, compiled
+// here and by the host checker alike; the kernels only decide who computes what.  No MFMA, no atomics with a return value, and
+// every count is an integer, so no launch shape or tiling can show in the result.
+//
+// Scoring is the hot loop: n_sets x iterations x m predicates of 14 float operations.  Lane = hypothesis: a workgroup holds 256
+// models in nine VGPRs a lane and up to kRansacRows rows of its set in LDS as 16-byte rows; all lanes read the same row (one
+// ds_read_b128 whose 64 addresses are equal: a broadcast, no bank conflict), the count stays in a register and leaves the lane
+// once, as an integer add to the hypothesis' score.  The other layout (lane = row, the model wave-uniform, ballot + popcount per
+// 64 rows) issues the same vector operations per predicate but pays a cross-lane step per hypothesis and wastes lanes on the
+// short lists (a few hundred rows) that a ratio test leaves; this one wastes lanes only below 256 iterations.
+#include "ransac_kernels.h"
+#include "ransac_math.h"
+
+namespace sift_hip {
+
+namespace {
+typedef float f4v __attribute__((ext_vector_type(4)));
+
+// the set of a row: the first s with off[s + 1] > row (sets may be empty); row >= off[0] and row < off[n_sets]
+__device__ __forceinline__ int set_of_row(const int64_t* __restrict__ off, int n_sets, long long row) {
+    int lo = 0, hi = n_sets - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid + 1] <= row) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+}  // namespace
+
+// one lane per (set, iteration): draw, gather four rows, solve in double
+__global__ __launch_bounds__(256) void ransac_hypothesis_kernel(const float* __restrict__ pts, const int64_t* __restrict__ off, int n_sets,
+                                                                uint32_t iterations, uint32_t seed, RansacHyp* __restrict__ hyp) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= (long long)n_sets * iterations) return;
+    const int set = (int)(gid / iterations);
+    const uint32_t it = (uint32_t)(gid % iterations);
+    const int64_t row0 = off[set], m = off[set + 1] - row0;
+    RansacHyp out;
+    for (int k = 0; k < 9; ++k) out.h[k] = 0.0f;
+    out.valid = 0;
+    if (m >= 4) {
+        uint32_t d[4];
+        float c[4][4];
+        ransac_draw(seed, (uint32_t)set, it, (uint32_t)m, d);
+        for (int k = 0; k < 4; ++k) {
+            const f4v r = *reinterpret_cast<const f4v*>(pts + 4 * (row0 + (int64_t)d[k]));
+            c[k][0] = r.x; c[k][1] = r.y; c[k][2] = r.z; c[k][3] = r.w;
+        }
+        out.valid = ransac_homography4(c, out.h) ? 1 : 0;
+    }
+    hyp[gid] = out;
+}
+
+__global__ __launch_bounds__(kRansacHyps) void ransac_score_kernel(const float* __restrict__ pts, const RansacHyp* __restrict__ hyp,
+                                                                   const RansacTile* __restrict__ tiles, uint32_t iterations, float thr2,
+                                                                   int32_t* __restrict__ scores) {
+    __shared__ __attribute__((aligned(16))) f4v rows[kRansacRows];
+    const RansacTile t = tiles[blockIdx.x];
+    const int n = t.row_hi - t.row_lo;   // <= kRansacRows
+    for (int i = threadIdx.x; i < n; i += kRansacHyps) rows[i] = *reinterpret_cast<const f4v*>(pts + 4 * ((size_t)t.row_lo + i));
+    __syncthreads();
+    const uint32_t it = (uint32_t)t.hyp0 + threadIdx.x;
+    if (it >= iterations) return;
+    const size_t slot = (size_t)t.set * iterations + it;
+    const RansacHyp me = hyp[slot];
+    if (!me.valid) return;
+    int count = 0;
+#pragma unroll 8
+    for (int i = 0; i < n; ++i) {
+        const f4v r = rows[i];
+        count += ransac_inlier(me.h, r.x, r.y, r.z, r.w, thr2) ? 1 : 0;
+    }
+    if (count) atomicAdd(&scores[slot], count);   // the result is not used: an add without return
+}
+
+// one workgroup per set: -1 into the scores of invalid hypotheses, the argmax under (score descending, iteration ascending)
+__global__ __launch_bounds__(256) void ransac_select_kernel(const RansacHyp* __restrict__ hyp, uint32_t iterations, int32_t* __restrict__ scores,
+                                                            sift_hip_homography* __restrict__ models) {
+    __shared__ int s_score[256];
+    __shared__ int s_iter[256];
+    const int tid = threadIdx.x;
+    const size_t base = (size_t)blockIdx.x * iterations;
+    int best = -1, best_it = 0x7fffffff;
+    for (uint32_t i = tid; i < iterations; i += 256) {   // ascending: a later iteration replaces only when strictly better
+        const int s = hyp[base + i].valid ? scores[base + i] : -1;
+        scores[base + i] = s;
+        if (s > best) { best = s; best_it = (int)i; }
+    }
+    s_score[tid] = best;
+    s_iter[tid] = best_it;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) {
+            const int os = s_score[tid + w], oi = s_iter[tid + w];
+            if (os > s_score[tid] || (os == s_score[tid] && oi < s_iter[tid])) { s_score[tid] = os; s_iter[tid] = oi; }
+        }
+        __syncthreads();
+    }
+    const bool any = s_score[0] >= 0;
+    const int win = s_iter[0];
+    sift_hip_homography* out = models + blockIdx.x;
+    if (tid < 9) out->h[tid] = any ? hyp[base + win].h[tid] : 0.0f;
+    if (tid == 9) out->inliers = any ? s_score[0] : 0;
+    if (tid == 10) out->iteration = any ? win : -1;
+    if (tid == 11) out->reserved = 0;
+}
+
+// one lane per row: the predicate under the winner of the row's set
+__global__ __launch_bounds__(256) void ransac_flags_kernel(const float* __restrict__ pts, const int64_t* __restrict__ off, int n_sets, long long rows,
+                                                           const sift_hip_homography* __restrict__ models, float thr2, uint8_t* __restrict__ inlier) {
+    const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (row >= rows) return;
+    bool in = false;
+    if (row >= off[0]) {
+        const sift_hip_homography* mdl = models + set_of_row(off, n_sets, row);
+        if (mdl->iteration >= 0) {
+            float h[9];
+            for (int k = 0; k < 9; ++k) h[k] = mdl->h[k];
+            const f4v r = *reinterpret_cast<const f4v*>(pts + 4 * (size_t)row);
+            in = ransac_inlier(h, r.x, r.y, r.z, r.w, thr2);
+        }
+    }
+    inlier[row] = in ? 1 : 0;
+}
+
+// one lane per record of the dense match list: the keypoints' image coordinates, (float)(x << octave) * coord_scale
+__global__ __launch_bounds__(256) void ransac_gather_kernel(const sift_hip_match_rec* __restrict__ recs, const int64_t* __restrict__ off, int n_pairs,
+                                                            long long rows, const sift_hip_keypoint* __restrict__ kp, const int* __restrict__ kp_row0,
+                                                            float coord_scale, float* __restrict__ pts) {
+    const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (row >= rows) return;
+    const int p = set_of_row(off, n_pairs, row);
+    const sift_hip_match_rec rec = recs[row];
+    const sift_hip_keypoint q = kp[(size_t)kp_row0[2 * p] + (size_t)rec.query], t = kp[(size_t)kp_row0[2 * p + 1] + (size_t)rec.train];
+    f4v o;
+    o.x = (float)((uint32_t)q.x << q.octave) * coord_scale;
+    o.y = (float)((uint32_t)q.y << q.octave) * coord_scale;
+    o.z = (float)((uint32_t)t.x << t.octave) * coord_scale;
+    o.w = (float)((uint32_t)t.y << t.octave) * coord_scale;
+    *reinterpret_cast<f4v*>(pts + 4 * (size_t)row) = o;
+}
+
+void launch_ransac_hypotheses(hipStream_t s, const float* d_pts, const int64_t* d_off, int n_sets, uint32_t iterations, uint32_t seed,
+                              RansacHyp* d_hyp) {
+    const long long n = (long long)n_sets * iterations;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(ransac_hypothesis_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_pts, d_off, n_sets, iterations, seed, d_hyp);
+}
+void launch_ransac_score(hipStream_t s, const float* d_pts, const RansacHyp* d_hyp, const RansacTile* d_tiles, int n_tiles, uint32_t iterations,
+                         float thr2, int32_t* d_scores) {
+    if (n_tiles <= 0) return;
+    hipLaunchKernelGGL(ransac_score_kernel, dim3((unsigned)n_tiles), dim3(kRansacHyps), 0, s, d_pts, d_hyp, d_tiles, iterations, thr2, d_scores);
+}
+void launch_ransac_select(hipStream_t s, const RansacHyp* d_hyp, int n_sets, uint32_t iterations, int32_t* d_scores, sift_hip_homography* d_models) {
+    if (n_sets <= 0) return;
+    hipLaunchKernelGGL(ransac_select_kernel, dim3((unsigned)n_sets), dim3(256), 0, s, d_hyp, iterations, d_scores, d_models);
+}
+void launch_ransac_flags(hipStream_t s, const float* d_pts, const int64_t* d_off, int n_sets, long long rows, const sift_hip_homography* d_models,
+                         float thr2, uint8_t* d_inlier) {
+    if (rows <= 0 || n_sets <= 0) return;
+    hipLaunchKernelGGL(ransac_flags_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, d_pts, d_off, n_sets, rows, d_models, thr2, d_inlier);
+}
+void launch_ransac_gather(hipStream_t s, const sift_hip_match_rec* d_recs, const int64_t* d_off, int n_pairs, long long rows,
+                          const sift_hip_keypoint* d_kp, const int* d_kp_row0, float coord_scale, float* d_pts) {
+    if (rows <= 0 || n_pairs <= 0) return;
+    hipLaunchKernelGGL(ransac_gather_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, d_recs, d_off, n_pairs, rows, d_kp, d_kp_row0,
+                       coord_scale, d_pts);
+}
+
+}  // namespace sift_hip

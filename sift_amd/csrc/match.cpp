@@ -3,44 +3,22 @@
 // context allocates and the context keeps - outside the batch arena, so a context that never matches allocates nothing here.
 #include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "common.h"
 #include "match_kernels.h"
+#include "ransac_kernels.h"   // match_result_on_device
 
 namespace sift_hip {
 
-namespace {
-struct Buf {   // device memory that only grows
-    void* p = nullptr;
-    size_t cap = 0;
-    void ensure(size_t bytes) {
-        if (bytes <= cap) return;
-        ApiGuard api;
-        if (p) SIFT_HIP_CHECK(hipFree(p));
-        p = nullptr;
-        cap = 0;
-        SIFT_HIP_CHECK(hipMalloc(&p, bytes + bytes / 4));
-        cap = bytes + bytes / 4;
-    }
-    void release() {
-        ApiGuard api;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <class T>
-    T* as() const { return reinterpret_cast<T*>(p); }
-};
-}  // namespace
-
 struct MatchState {
-    Buf d_desc, d_kp;                 // staging of descriptor rows / keypoint records that arrive in host memory
-    Buf d_norm, d_valid;              // n(a) and the valid flag of every row
-    Buf d_tiles, d_blocks, d_pairs;   // the launch tables
-    Buf d_part;                       // partial top-2s, kMatchQ per tile
-    Buf d_idx, d_dist;                // top-2 of every query row (forward rows first, then the cross-check's reverse rows)
-    Buf d_seg, d_out, d_counts;       // records per pair segment, the dense list, per-pair counts
+    ScratchBuf d_desc, d_kp;                 // staging of descriptor rows / keypoint records that arrive in host memory
+    ScratchBuf d_norm, d_valid;              // n(a) and the valid flag of every row
+    ScratchBuf d_tiles, d_blocks, d_pairs;   // the launch tables
+    ScratchBuf d_part;                       // partial top-2s, kMatchQ per tile
+    ScratchBuf d_idx, d_dist;                // top-2 of every query row (forward rows first, then the cross-check's reverse rows)
+    ScratchBuf d_seg, d_out, d_counts;       // records per pair segment, the dense list, per-pair counts
     void* h_tables = nullptr;         // page-locked image of the three tables (the copy is asynchronous)
     size_t h_cap = 0;
     std::vector<int32_t> counts;
@@ -48,7 +26,7 @@ struct MatchState {
 
 void match_state_free(MatchState* st) {
     if (!st) return;
-    for (Buf* b : {&st->d_desc, &st->d_kp, &st->d_norm, &st->d_valid, &st->d_tiles, &st->d_blocks, &st->d_pairs, &st->d_part, &st->d_idx,
+    for (ScratchBuf* b : {&st->d_desc, &st->d_kp, &st->d_norm, &st->d_valid, &st->d_tiles, &st->d_blocks, &st->d_pairs, &st->d_part, &st->d_idx,
                    &st->d_dist, &st->d_seg, &st->d_out, &st->d_counts})
         b->release();
     if (st->h_tables) {
@@ -77,6 +55,9 @@ struct Job {
     int64_t* total;
     char* err;
     int errlen;
+    // sift_hip_result_verify goes on with the list where it is: the dense records on the device, the pairs' counts (both null: not asked)
+    const sift_hip_match_rec** d_recs_out = nullptr;
+    int32_t* host_counts_out = nullptr;
 };
 
 int fail(const Job& j, const char* msg) {
@@ -149,6 +130,8 @@ int run(void* arg) {
 
     if (j.counts) std::fill(j.counts, j.counts + j.n_pairs, 0);
     if (j.total) *j.total = 0;
+    if (j.d_recs_out) *j.d_recs_out = nullptr;
+    if (j.host_counts_out) std::fill(j.host_counts_out, j.host_counts_out + j.n_pairs, 0);
     if (fwd_rows == 0) return SIFT_HIP_OK;
 
     if (!*v.state) *v.state = new MatchState();
@@ -260,10 +243,29 @@ int run(void* arg) {
     match_wait(j.c);
     if (j.counts) std::copy(st.counts.begin(), st.counts.end(), j.counts);
     if (j.total) *j.total = total;
+    if (j.d_recs_out) *j.d_recs_out = d_out;
+    if (j.host_counts_out) std::copy(st.counts.begin(), st.counts.end(), j.host_counts_out);
     return SIFT_HIP_OK;
 }
 
 }  // namespace
+}  // namespace sift_hip
+
+namespace sift_hip {
+int match_result_on_device(sift_hip_ctx* c, const char* who, int n_pairs, const int32_t* pair_q, const int32_t* pair_t,
+                           const sift_hip_match_params* params, sift_hip_match_rec* recs, int32_t* counts, int64_t* total,
+                           const sift_hip_match_rec** d_recs, int32_t* host_counts, char* err, int errlen) {
+    const MatchCtxView v = match_ctx_view(c);
+    if (!v.have_result) {
+        match_set_err(err, errlen, (std::string(who) + ": the context holds no results").c_str());
+        return SIFT_HIP_EINVAL;
+    }
+    std::vector<int64_t> offsets((size_t)v.n_images + 1, 0);
+    for (int i = 0; i < v.n_images; ++i) offsets[(size_t)i + 1] = offsets[(size_t)i] + v.counts[i];
+    Job j{c, v.d_desc, v.d_kp, true, v.n_images, offsets.data(), n_pairs, pair_q, pair_t, params, nullptr, nullptr, recs, counts, total, err, errlen,
+          d_recs, host_counts};
+    return match_guarded(err, errlen, run, &j);
+}
 }  // namespace sift_hip
 
 using namespace sift_hip;
@@ -290,12 +292,7 @@ int sift_hip_result_match(sift_hip_ctx* c, int n_pairs, const int32_t* pair_q, c
                           sift_hip_match_rec* recs, int32_t* counts, int64_t* total, char* err, int errlen) {
     if (!c) { match_set_err(err, errlen, "sift_hip_result_match: no context (matching runs on the GPU only)"); return SIFT_HIP_EINVAL; }
     if (!params) { match_set_err(err, errlen, "sift_hip_result_match: no parameters"); return SIFT_HIP_EINVAL; }
-    const MatchCtxView v = match_ctx_view(c);
-    if (!v.have_result) { match_set_err(err, errlen, "sift_hip_result_match: the context holds no results"); return SIFT_HIP_EINVAL; }
-    std::vector<int64_t> offsets((size_t)v.n_images + 1, 0);
-    for (int i = 0; i < v.n_images; ++i) offsets[(size_t)i + 1] = offsets[(size_t)i] + v.counts[i];
-    Job j{c, v.d_desc, v.d_kp, true, v.n_images, offsets.data(), n_pairs, pair_q, pair_t, params, nullptr, nullptr, recs, counts, total, err, errlen};
-    return match_guarded(err, errlen, run, &j);
+    return match_result_on_device(c, "sift_hip_result_match", n_pairs, pair_q, pair_t, params, recs, counts, total, nullptr, nullptr, err, errlen);
 }
 
 }  // extern "C"

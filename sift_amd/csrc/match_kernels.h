@@ -47,6 +47,29 @@ void launch_match_pack(hipStream_t s, const sift_hip_match_rec* d_seg, const Mat
                        sift_hip_match_rec* d_out);
 void tu_touch_match(hipStream_t s);
 
+// scratch of the matcher and of the geometric verification (ransac.cpp): device memory that only grows, kept with the context
+struct ScratchBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    void ensure(size_t bytes) {
+        if (bytes <= cap) return;
+        ApiGuard api;
+        if (p) SIFT_HIP_CHECK(hipFree(p));
+        p = nullptr;
+        cap = 0;
+        SIFT_HIP_CHECK(hipMalloc(&p, bytes + bytes / 4));
+        cap = bytes + bytes / 4;
+    }
+    void release() {
+        ApiGuard api;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <class T>
+    T* as() const { return reinterpret_cast<T*>(p); }
+};
+
 // ---- the context as match.cpp sees it (context.cpp) ---------------------------------------------------------
 struct MatchState;                       // scratch of the matcher, owned by the context once the first match call made it
 void match_state_free(MatchState* st);   // match.cpp; sift_hip_destroy calls it

@@ -1,0 +1,172 @@
+"""Geometric verification on the GPU, measured (bench.py measures extraction and is left alone).
+
+Cases, all at --iterations hypotheses per set (2048) and a 3 px threshold: (a) the match list of frames 1 and 2 of the bench
+batch (ratio 0.8), its coordinates resident on the device, through sift_hip_ransac_homography; (b) the 31 consecutive pairs of
+the 32-frame batch through ONE sift_hip_result_verify call (matching + coordinates + RANSAC, records, flags and models to the
+host), beside sift_hip_result_match alone and the RANSAC alone on the same lists; (c) one synthetic list of 20 000 rows, where
+the scoring kernel and not the launches sets the time.  Comparators on the same rows: the torch formulation on the same GPU -
+SCORING ONLY, given a table of models: batched H @ pts, the division-free comparison, sum, argmax (no sampling, no solve: that
+favours it) - alternating with the library's arm in the same run, and the host loop (hostmath_ransac_homography) on one core.
+The models and flags of every case are compared bit for bit with the host loop.
+
+Timing: a warm-up, then --reps repetitions of each arm in turn; median and min - max of the host time around each call (the
+library's calls return when the result is in place; the torch arm ends in a synchronize).  predicates/s = sets' rows x
+iterations / time (invalid hypotheses are not scored, so the work done is smaller: "valid_share").
+
+    python tools/ransac_bench.py [--reps 20] [--frames 32] [--out profiles/ransac_bench.txt]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def stats(ms):
+    return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4), "reps": len(ms)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--frames", type=int, default=32)
+    ap.add_argument("--iterations", type=int, default=2048)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+
+    import torch
+    import ransac_ref as R
+    from sift_amd import _lib
+    from sift_amd.sift import Context, K_SQRT2
+    from sift_amd.synthetic import synth_batch
+
+    lines = []
+    its, thr = args.iterations, 3.0
+
+    def emit(obj):
+        line = json.dumps(obj)
+        print(line, flush=True)
+        lines.append(line)
+
+    def timed(fn, reps):
+        ms = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return stats(ms)
+
+    def race(fused, comparator):
+        for _ in range(args.warmup):
+            fused()
+            comparator()
+        torch.cuda.synchronize()
+        f_ms, t_ms = [], []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            fused()
+            f_ms.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            comparator()
+            torch.cuda.synchronize()
+            t_ms.append((time.perf_counter() - t0) * 1e3)
+        return stats(f_ms), stats(t_ms)
+
+    def torch_score(tpts, toff, hs):
+        """Per set: scores of `hs` [I, 3, 3] over the set's rows, and the argmax.  float32 throughout."""
+        out = []
+        for s in range(len(toff) - 1):
+            p = tpts[toff[s]:toff[s + 1]]
+            if p.shape[0] == 0:
+                continue
+            q = torch.cat([p[:, :2], torch.ones_like(p[:, :1])], dim=1)
+            xyw = hs @ q.T                                               # [I, 3, m]
+            ex, ey = xyw[:, 0] - p[:, 2] * xyw[:, 2], xyw[:, 1] - p[:, 3] * xyw[:, 2]
+            inl = (xyw[:, 2] > 0) & (ex * ex + ey * ey <= (thr * thr) * xyw[:, 2] * xyw[:, 2])
+            out.append(torch.argmax(inl.sum(dim=1)))
+        return out
+
+    def coords(kp, row0, idx):
+        k = kp[row0 + idx]
+        return np.stack([k["x"].astype(np.int64) << k["octave"], k["y"].astype(np.int64) << k["octave"]], axis=1).astype(np.float32)
+
+    def case(name, ctx, pts, off, extra):
+        """RANSAC alone on rows resident on the device, against the torch scoring and the host loop."""
+        n_sets = off.size - 1
+        dpts = torch.from_numpy(pts).cuda()
+        dm = torch.zeros((n_sets, 12), dtype=torch.int32, device="cuda")
+        df = torch.zeros((max(pts.shape[0], 1),), dtype=torch.uint8, device="cuda")
+        hs = (torch.eye(3, device="cuda")[None] + 1e-4 * torch.randn((its, 3, 3), device="cuda")).contiguous()
+        toff = off.tolist()
+        torch.cuda.synchronize()
+        f, t = race(lambda: ctx.ransac_homography(dpts, off, its, thr, 0, models_out=dm, inlier_out=df), lambda: torch_score(dpts, toff, hs))
+        host = timed(lambda: R.ransac(pts, off, its, thr, 0), 3)
+        want = R.ransac(pts, off, its, thr, 0)
+        ok = dm.cpu().numpy().tobytes() == want[0].tobytes() and df.cpu().numpy()[:pts.shape[0]].tobytes() == want[1].tobytes()
+        pred = float(pts.shape[0]) * its
+        emit({"case": name, "sets": int(n_sets), "rows": int(pts.shape[0]), "iterations": its, "valid_share": round(float((want[2] >= 0).mean()), 3),
+              "inliers": want[0]["inliers"].tolist()[:4], "bitwise_equal_to_host_loop": bool(ok), "gpu": f, "torch_scoring_only": t,
+              "host_loop_one_core": host, "gpu_gpred_per_s": round(pred / (f["median_ms"] * 1e-3) / 1e9, 2),
+              "speedup_vs_torch": round(t["median_ms"] / f["median_ms"], 2), "speedup_vs_host_loop": round(host["median_ms"] / f["median_ms"], 1),
+              **extra})
+
+    ctx = Context(0)
+    n = args.frames
+    ctx.calculate_batch(synth_batch(n, 1920, 1080), _lib.Params(3, 4, 1.6, K_SQRT2, 0))
+    cnt = ctx.counts()
+    row0 = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+    kp, _ = ctx.results()
+
+    # ---- (a): two 1080p frames' match list ----
+    rec, counts = ctx.match_images([(0, 1)], 0.8, False)
+    pts = np.concatenate([coords(kp, row0[0], rec["query"]), coords(kp, row0[1], rec["train"])], axis=1)
+    case("a: match list of frames 1 and 2 of the bench batch (ratio 0.8), rows on the device, sift_hip_ransac_homography", ctx, pts,
+         np.array([0, pts.shape[0]], np.int64), {"keypoints": [int(cnt[0]), int(cnt[1])]})
+
+    # ---- (b): 31 pairs in one call ----
+    pairs = [(i, i + 1) for i in range(n - 1)]
+    for _ in range(args.warmup):
+        ctx.verify_images(pairs, 0.8, False, its, thr, 0)
+        ctx.match_images(pairs, 0.8, False)
+    v_ms, m_ms = [], []
+    for _ in range(args.reps):
+        t0 = time.perf_counter()
+        ctx.verify_images(pairs, 0.8, False, its, thr, 0)
+        v_ms.append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter()
+        ctx.match_images(pairs, 0.8, False)
+        m_ms.append((time.perf_counter() - t0) * 1e3)
+    rec, counts, models, flags = ctx.verify_images(pairs, 0.8, False, its, thr, 0)
+    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    pts = np.zeros((rec.size, 4), np.float32)
+    for p, (a, b) in enumerate(pairs):
+        r = rec[off[p]:off[p + 1]]
+        pts[off[p]:off[p + 1]] = np.concatenate([coords(kp, row0[a], r["query"]), coords(kp, row0[b], r["train"])], axis=1)
+    want = R.ransac(pts, off, its, thr, 0)
+    ok = models.astype(R.MODEL_DTYPE).tobytes() == want[0].tobytes() and flags.tobytes() == want[1].tobytes()
+    emit({"case": f"b: the {len(pairs)} consecutive pairs of the batch in one sift_hip_result_verify call (ratio 0.8), records, flags and models to the host",
+          "matches": int(rec.size), "iterations": its, "bitwise_equal_to_host_loop": bool(ok), "result_verify": stats(v_ms),
+          "result_match_alone": stats(m_ms), "difference_of_medians_ms": round(statistics.median(v_ms) - statistics.median(m_ms), 4)})
+    case("b, the RANSAC alone: the same 31 lists as the sets of one sift_hip_ransac_homography call, rows on the device", ctx, pts, off, {})
+
+    # ---- (c): one long list ----
+    rows, _ = R.projective_rows(np.random.default_rng(0), 20000)
+    case("c: 20 000 synthetic correspondences (60 % outliers), rows on the device", ctx, rows, np.array([0, 20000], np.int64), {})
+    ctx.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("# tools/ransac_bench.py: GPU RANSAC homography against the torch scoring formulation (same GPU, alternating) and the host loop (ms on the host around each call)\n")
+            f.write("# solver: largest deviation of ransac_homography4 from numpy's float64 8x8 solution over tests/test_ransac_host.py's samples, both scaled by their largest entry: 1.16e-08\n")
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
