@@ -2,7 +2,7 @@
 // sift::Matcher::verify(): a RANSAC homography over the matches (include/sift/match.hpp; extensions, the reference has neither).
 // inliers.txt holds the lines of matches.txt that agree with the model.
 //   g++ -std=c++17 -pthread -Iinclude examples/sift_verify.cpp -Lsift_amd/lib -lsift_hip -Wl,-rpath,$PWD/sift_amd/lib -o sift_verify
-//   ./sift_verify a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0]
+//   ./sift_verify a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [refine=0]
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -36,7 +36,7 @@ static void write_matches(const char* path, const std::vector<sift::Match>& matc
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::cerr << "usage: " << argv[0]
-                  << " a.{pgm,ppm,png,jpg} b.{...} [octaves] [dogsPerEpoch] [ratio] [crossCheck] [iterations] [threshold] [seed]\n";
+                  << " a.{pgm,ppm,png,jpg} b.{...} [octaves] [dogsPerEpoch] [ratio] [crossCheck] [iterations] [threshold] [seed] [refine]\n";
         return 1;
     }
     const u16_t octaves = argc > 3 ? (u16_t)std::atoi(argv[3]) : 4;
@@ -46,17 +46,19 @@ int main(int argc, char** argv) {
     const unsigned iterations = argc > 7 ? (unsigned)std::atoi(argv[7]) : 2048u;
     const float threshold = argc > 8 ? (float)std::atof(argv[8]) : 3.0f;
     const unsigned seed = argc > 9 ? (unsigned)std::atoi(argv[9]) : 0u;
+    const unsigned refine = argc > 10 ? (unsigned)std::atoi(argv[10]) : 0u;   // rounds of least-squares re-estimation over the inliers
     try {
         sift::Sift sift(dogsPerEpoch, octaves, 1.6f, std::sqrt(2.0f), false);
         const std::vector<sift::InterestPoint> a = points_of(sift, argv[1]);
         const std::vector<sift::InterestPoint> b = points_of(sift, argv[2]);
         sift::Matcher matcher;
         const std::vector<sift::Match> matches = matcher.match(a, b, ratio, crossCheck);
-        const sift::Homography model = matcher.verify(a, b, matches, iterations, threshold, seed);
+        const sift::Homography model = matcher.verify(a, b, matches, iterations, threshold, seed, false, refine);
         write_matches("matches.txt", matches, nullptr);
         write_matches("inliers.txt", matches, &model.inlier);
         std::cout << a.size() << " and " << b.size() << " interest points, " << matches.size() << " matches -> matches.txt, " << model.inliers
                   << " inliers -> inliers.txt\n";
+        if (refine) std::cout << "refined " << model.refined << " rounds\n";
         if (model.iteration < 0) {
             std::cout << "no homography\n";
         } else {

@@ -19,9 +19,11 @@ struct Match {
 };
 
 struct Homography {
-    f32_t h[9] = {};                     // row-major, query image -> train image: (tx, ty, 1) ~ H (qx, qy, 1); the best minimal-sample model
+    f32_t h[9] = {};                     // row-major, query image -> train image: (tx, ty, 1) ~ H (qx, qy, 1); the best minimal-sample model,
+                                         // re-estimated over its inliers when Matcher::verify is given refine > 0
     int inliers = 0;
     int iteration = -1;                  // the winning hypothesis; -1: no model (fewer than four matches, or every sample degenerate)
+    int refined = 0;                     // refinement rounds accepted, 0 .. refine
     std::vector<unsigned char> inlier;   // one flag per match handed to Matcher::verify
 };
 
@@ -74,10 +76,11 @@ public:
 
     // The geometric check of a match list (include/sift_hip.h, "geometric verification"): the best four-point homography
     // from the query image to the train image over the matches' image coordinates, loc * 2^octave (halved when the points
-    // come from a subpixel run), and one flag per match.  Throws std::invalid_argument for iterations outside 1 .. 65536 or a
-    // threshold that is not finite and positive.
+    // come from a subpixel run), and one flag per match.  refine: rounds of least-squares re-estimation of the winner over its
+    // own inliers, 0 .. 8 (0: the minimal-sample model; the inlier count never decreases).  Throws std::invalid_argument for
+    // iterations outside 1 .. 65536, a threshold that is not finite and positive, or refine above 8.
     Homography verify(const std::vector<InterestPoint>& query, const std::vector<InterestPoint>& train, const std::vector<Match>& matches,
-                      unsigned iterations = 2048, f32_t threshold = 3.0f, unsigned seed = 0, bool subpixel = false) {
+                      unsigned iterations = 2048, f32_t threshold = 3.0f, unsigned seed = 0, bool subpixel = false, unsigned refine = 0) {
         const f32_t scale = subpixel ? 0.5f : 1.0f;
         _pts.resize(matches.size() * 4);
         for (size_t i = 0; i < matches.size(); ++i) {
@@ -93,6 +96,7 @@ public:
         prm.iterations = iterations;
         prm.seed = seed;
         prm.threshold = threshold;
+        prm.refine = refine;
         sift_hip_homography model{};
         Homography out;
         out.inlier.assign(matches.size(), 0);
@@ -103,6 +107,7 @@ public:
         for (int k = 0; k < 9; ++k) out.h[k] = model.h[k];
         out.inliers = model.inliers;
         out.iteration = model.iteration;
+        out.refined = model.refined;
         return out;
     }
 

@@ -252,35 +252,51 @@ int sift_hip_result_match(sift_hip_ctx* ctx, int n_pairs, const int32_t* pair_q,
  *   selection  score = inliers among ALL m rows, or -1 for an invalid hypothesis; the winner has the highest score, the lowest i
  *              among equals.  No valid hypothesis, or m < 4: iteration -1, inliers 0, h all +0.0f, every flag 0.
  * Scores are integers, so the result does not depend on how rows or hypotheses are tiled, split over workgroups or reduced.
- * The returned H is the best MINIMAL-SAMPLE model: there is no least-squares refit over the inliers (a follow-up: its sums
- * would need a fixed order), no adaptive early stop and no other model. */
+ * With refine == 0 the returned H is the best MINIMAL-SAMPLE model.  With refine = 1 .. 8 the winner is then re-estimated from
+ * its own inliers, at most `refine` rounds (sift_amd/csrc/ransac_refine_math.h defines them bit for bit; the host loop is
+ * hostmath_refine_homography).  A round: n = the inliers of h; a normalised inhomogeneous DLT over them in double (centroids
+ * and power-of-two scales from the moments, the 22 sums of the 8 x 8 normal equations, Gaussian elimination with partial
+ * pivoting, denormalisation, division by the entry of largest magnitude, W > 0 at the query centroid, nine floats) gives h';
+ * c' = the inliers of h' among all rows.  The round fails - h stays, the rounds end - when n < 4, a side's spread is zero or not
+ * finite, a pivot is zero or not finite, or an entry is not finite.  h' is accepted when c' >= c, and another round follows
+ * only when c' > c: the inlier count never decreases.  Every floating-point sum over rows has a FIXED ORDER: 256 partials
+ * (partial p: rows i = p mod 256, ascending, from +0.0, inliers only), combined by the adjacent pairwise tree - so the result
+ * stays bit-defined.  There is no adaptive early stop and no other model. */
 typedef struct sift_hip_ransac_params {
     uint32_t iterations;  /* hypotheses per set, 1 .. 65536 */
     uint32_t seed;
     float threshold;      /* pixels, finite and > 0 */
-    uint32_t reserved;
+    uint32_t refine;      /* refinement rounds over the winner's inliers, 0 .. 8; 0: none (the minimal-sample model) */
 } sift_hip_ransac_params;
 typedef struct sift_hip_homography {
     float h[9];           /* row-major */
-    int32_t inliers;      /* score of the winner = number of flags set */
+    int32_t inliers;      /* inliers of h = number of flags set (refine 0: the score of the winner) */
     int32_t iteration;    /* the winning hypothesis; -1: none */
-    int32_t reserved;
+    int32_t refined;      /* refinement rounds accepted, 0 .. refine */
 } sift_hip_homography;
 /* pts: the sets' rows back to back (host memory, or device memory aligned to 16 bytes); offsets as for the match calls
  * (n_sets + 1 entries, host memory).  models: n_sets records; inlier (may be NULL): one byte per row, 1 = inlier of its set's winner; scores (may be
  * NULL): n_sets x iterations int32, the score of every hypothesis.  The three may each be host or device memory.  Empty sets
  * are legal.  All sets of a call share one launch of each kernel.  SIFT_HIP_EINVAL for iterations 0 or above 65536, a
- * threshold that is not finite and positive, or bad offsets.  Runs on the context's stream, returns when the results are in
+ * threshold that is not finite and positive, refine above 8, or bad offsets.  With refine > 0 the flags are the predicate
+ * under the refined model; `iteration` and `scores` are those of the hypotheses, whatever refine is.  Runs on the context's stream, returns when the results are in
  * place; scratch memory is allocated by the first call and kept with the context. */
 int sift_hip_ransac_homography(sift_hip_ctx* ctx, const float* pts, int n_sets, const int64_t* offsets,
                                const sift_hip_ransac_params* params, sift_hip_homography* models, uint8_t* inlier,
                                int32_t* scores, char* err, int errlen);
+/* The refinement alone, from models the caller supplies (one carried over from the previous frame pair, say): no sampling.
+ * models: n_sets records, in and out.  A model with iteration >= 0 starts from its h with the score c = its inliers under the
+ * predicate, runs at most `rounds` rounds (0 .. 8; 0 only counts) and gets h, inliers (the count under the final h) and
+ * refined rewritten; iteration stays.  A model with iteration -1 is left alone and all its flags are 0.  pts, offsets, inlier
+ * and the memory rules as for sift_hip_ransac_homography; models may be host or device memory.  One launch for all sets. */
+int sift_hip_refine_homography(sift_hip_ctx* ctx, const float* pts, int n_sets, const int64_t* offsets, float threshold,
+                               int rounds, sift_hip_homography* models, uint8_t* inlier, char* err, int errlen);
 /* sift_hip_result_match followed by the verification of its lists, on the device-resident results: pair p is set p, row i of
  * the set is record i of the pair, with qx = (float)(x << octave) of the record's query keypoint (qy, tx, ty likewise), times
  * 0.5f when the last batch ran with subpixel (both exact in float) - built on the GPU.  recs, counts, total as
  * sift_hip_result_match delivers them; models: n_pairs records; inlier (may be NULL): one byte per record of `recs`.  Bit for
  * bit the result of sift_hip_result_match plus sift_hip_ransac_homography on those coordinates; only records, flags and
- * models leave the GPU.  recs, models and inlier may each be host or device memory. */
+ * models leave the GPU (ransac_params->refine included).  recs, models and inlier may each be host or device memory. */
 int sift_hip_result_verify(sift_hip_ctx* ctx, int n_pairs, const int32_t* pair_q, const int32_t* pair_t,
                            const sift_hip_match_params* match_params, const sift_hip_ransac_params* ransac_params,
                            sift_hip_match_rec* recs, int32_t* counts, int64_t* total, sift_hip_homography* models,

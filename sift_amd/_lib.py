@@ -36,7 +36,7 @@ SYMBOLS = [
     "sift_hip_image_info", "sift_hip_image_read_band0", "sift_hip_image_read_bgr8", "sift_hip_png_write_bgr8",
     "sift_hip_rotated_rect_points", "sift_hip_overlay_box", "sift_hip_overlay_draw",
     "sift_hip_knn2", "sift_hip_match", "sift_hip_result_match",
-    "sift_hip_ransac_homography", "sift_hip_result_verify",
+    "sift_hip_ransac_homography", "sift_hip_result_verify", "sift_hip_refine_homography",
 ]
 
 
@@ -54,10 +54,10 @@ assert MATCH_DTYPE.itemsize == 16
 
 
 class RansacParams(C.Structure):
-    _fields_ = [("iterations", C.c_uint32), ("seed", C.c_uint32), ("threshold", C.c_float), ("reserved", C.c_uint32)]
+    _fields_ = [("iterations", C.c_uint32), ("seed", C.c_uint32), ("threshold", C.c_float), ("refine", C.c_uint32)]
 
 
-HOMOGRAPHY_DTYPE = np.dtype([("h", "<f4", (9,)), ("inliers", "<i4"), ("iteration", "<i4"), ("reserved", "<i4")])
+HOMOGRAPHY_DTYPE = np.dtype([("h", "<f4", (9,)), ("inliers", "<i4"), ("iteration", "<i4"), ("refined", "<i4")])
 assert HOMOGRAPHY_DTYPE.itemsize == 48
 
 KEYPOINT_DTYPE = np.dtype([("scale", "<f4"), ("orientation", "<f4"), ("x", "<u2"), ("y", "<u2"),
@@ -193,6 +193,7 @@ def load():
     L.sift_hip_result_match.argtypes = [vp, ci, i32p, i32p, C.POINTER(MatchParams), vp, i32p, C.POINTER(C.c_int64), cs, ci]
     # pts, models, inlier and scores may be host or device memory too
     L.sift_hip_ransac_homography.argtypes = [vp, vp, ci, i64p, C.POINTER(RansacParams), vp, vp, vp, cs, ci]
+    L.sift_hip_refine_homography.argtypes = [vp, vp, ci, i64p, C.c_float, ci, vp, vp, cs, ci]
     L.sift_hip_result_verify.argtypes = [vp, ci, i32p, i32p, C.POINTER(MatchParams), C.POINTER(RansacParams), vp, i32p, C.POINTER(C.c_int64),
                                          vp, vp, cs, ci]
     _lib = L

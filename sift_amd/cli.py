@@ -3,7 +3,7 @@ overlay :59-76) on top of the GPU path — SURVEY.md §8(f) rows 1-3.
 
     python -m sift_amd.cli -i image.pgm [-s 1.6] [-k 1.41421354] [-o 4] [-d 3] [-p 0] [-r 1]
     python -m sift_amd.cli -i a.pgm --match b.pgm [--ratio 0.8] [--cross-check]      (an extension: matches.txt)
-    python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--iterations 2048] [--threshold 3] [--seed 0]   (... and inliers.txt)
+    python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--iterations 2048] [--threshold 3] [--seed 0] [--refine 0]   (... and inliers.txt)
 
 Image ingest follows Vigra's scalar import: band 0 of multi-band files, values unscaled.  PGM,
 PPM, PNG and JPEG are decoded by the library itself (sift_amd/csrc/image_io.cpp, jpeg_decode.cpp: no PIL, no OpenCV, no libjpeg).
@@ -136,9 +136,14 @@ def main(argv=None) -> int:
     ap.add_argument("--iterations", type=int, default=2048, help="hypotheses of --verify (1 .. 65536)")
     ap.add_argument("--threshold", type=float, default=3.0, help="inlier threshold of --verify in pixels")
     ap.add_argument("--seed", type=int, default=0, help="seed of --verify's sampling")
+    ap.add_argument("--refine", type=int, default=0, help="with --verify: rounds of least-squares re-estimation over the inliers (0 .. 8)")
     args = ap.parse_args(argv)
     if args.verify and not args.match:
         ap.error("--verify needs --match")
+    if args.refine and not args.verify:
+        ap.error("--refine needs --verify")
+    if not 0 <= args.refine <= 8:
+        ap.error("--refine must be 0 .. 8")
     path = args.img or args.img_pos
     if not path:
         ap.print_help()
@@ -157,12 +162,15 @@ def main(argv=None) -> int:
             if not args.verify:
                 matches = sift.match(points, points2, args.ratio, args.cross_check)
             else:
-                matches, model, inlier = sift.verify(points, points2, args.ratio, args.cross_check, args.iterations, args.threshold, args.seed)
+                matches, model, inlier = sift.verify(points, points2, args.ratio, args.cross_check, args.iterations, args.threshold, args.seed,
+                                                     args.refine)
             write_matches("matches.txt", matches)
             print(f"{len(points2)} interest points in {args.match}, {len(matches)} matches")
             if args.verify:
                 write_matches("inliers.txt", matches[inlier != 0])
                 print(f"{int(model['inliers'])} inliers -> inliers.txt")
+                if args.refine:
+                    print(f"refined {int(model['refined'])} rounds")
                 if model["iteration"] < 0:
                     print("no homography")
                 else:

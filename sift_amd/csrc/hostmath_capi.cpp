@@ -9,6 +9,7 @@
 #include "hist_bins.h"
 #include "linalg3.h"
 #include "ransac_math.h"
+#include "ransac_refine_math.h"
 #include "../../include/sift_hip.h"   // sift_hip_homography
 
 extern "C" {
@@ -169,5 +170,132 @@ void hostmath_ransac_homography(const float* pts, int n_sets, const int64_t* off
             for (int64_t i = 0; i < m; ++i)
                 inlier[offsets[s] + i] = best.iteration >= 0 && sift_hip::ransac_inlier(best.h, p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], thr2) ? 1 : 0;
     }
+}
+
+}  // extern "C"
+
+// ---- the refinement as ransac_refine_math.h defines it, in plain loops: what ransac_refine_kernel must reproduce bit for bit.
+namespace {
+using namespace sift_hip;
+int refine_count(const float* p, int64_t m, const float (&h)[9], float thr2) {
+    int c = 0;
+    for (int64_t i = 0; i < m; ++i) c += ransac_inlier(h, p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], thr2) ? 1 : 0;
+    return c;
+}
+// K fixed-order sums over the inliers of h: 256 strided partials from +0.0, rows ascending, then the adjacent tree
+template <int K, typename Terms>
+int refine_fixed_sums(const float* p, int64_t m, const float (&h)[9], float thr2, Terms terms, double (&out)[K]) {
+    double s[K][kRefineLanes];
+    for (int k = 0; k < K; ++k)
+        for (int l = 0; l < kRefineLanes; ++l) s[k][l] = 0.0;
+    int n = 0;
+    for (int64_t i = 0; i < m; ++i) {
+        if (!ransac_inlier(h, p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], thr2)) continue;
+        double t[K];
+        terms(p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], t);
+        for (int k = 0; k < K; ++k) s[k][i % kRefineLanes] = s[k][i % kRefineLanes] + t[k];
+        ++n;
+    }
+    for (int k = 0; k < K; ++k) out[k] = refine_tree256(s[k]);
+    return n;
+}
+int refine_moments(const float* p, int64_t m, const float (&h)[9], float thr2, double (&mom)[kRefineMoments]) {
+    return refine_fixed_sums<kRefineMoments>(
+        p, m, h, thr2, [](float a, float b, float c, float d, double (&t)[kRefineMoments]) { refine_moment_terms(a, b, c, d, t); }, mom);
+}
+void refine_normal_sums(const float* p, int64_t m, const float (&h)[9], float thr2, const RefineNorm& nm, double (&s)[kRefineSums]) {
+    refine_fixed_sums<kRefineSums>(
+        p, m, h, thr2, [&nm](float a, float b, float c, float d, double (&t)[kRefineSums]) { refine_normal_terms(nm, a, b, c, d, t); }, s);
+}
+// one round: h -> h2; false when the round fails.  n = the inliers of h (its score).
+bool refine_round(const float* p, int64_t m, const float (&h)[9], float thr2, float (&h2)[9], int& n) {
+    double mom[kRefineMoments], s[kRefineSums], M[72], x[8];
+    RefineNorm nm;
+    n = refine_moments(p, m, h, thr2, mom);
+    if (n < 4 || !refine_normalisation(mom, n, nm)) return false;
+    refine_normal_sums(p, m, h, thr2, nm, s);
+    refine_system(s, n, M);
+    if (!refine_solve8(M, x)) return false;
+    for (int k = 0; k < 9; ++k) h2[k] = h[k];
+    return refine_denormalise(x, nm, h2);
+}
+// all rounds of one set: the model in place, its inlier count and the rounds accepted
+void refine_set(const float* p, int64_t m, float thr2, int rounds, float (&h)[9], int32_t& inliers, int32_t& refined) {
+    refined = 0;
+    int c = refine_count(p, m, h, thr2);
+    for (int r = 0; r < rounds; ++r) {
+        float h2[9];
+        int n;
+        if (!refine_round(p, m, h, thr2, h2, n)) break;   // n == c: the score is the inlier count
+        const int c2 = refine_count(p, m, h2, thr2);
+        if (c2 < c) break;
+        for (int k = 0; k < 9; ++k) h[k] = h2[k];
+        ++refined;
+        if (c2 == c) break;
+        c = c2;
+    }
+    inliers = c;
+}
+void refine_models(const float* pts, int n_sets, const int64_t* offsets, float thr, int rounds, sift_hip_homography* models, uint8_t* inlier) {
+    const float thr2 = thr * thr;
+    if (inlier && n_sets > 0)
+        for (int64_t i = 0; i < offsets[0]; ++i) inlier[i] = 0;
+    for (int s = 0; s < n_sets; ++s) {
+        const float* p = pts + 4 * offsets[s];
+        const int64_t m = offsets[s + 1] - offsets[s];
+        sift_hip_homography& mdl = models[s];
+        if (mdl.iteration >= 0) refine_set(p, m, thr2, rounds, mdl.h, mdl.inliers, mdl.refined);   // a model that is none is left alone
+        if (inlier)
+            for (int64_t i = 0; i < m; ++i)
+                inlier[offsets[s] + i] = mdl.iteration >= 0 && ransac_inlier(mdl.h, p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], thr2) ? 1 : 0;
+    }
+}
+}  // namespace
+
+extern "C" {
+// models: in-out; rounds 0 .. 8 (0 only counts the inliers of the given models)
+void hostmath_refine_homography(const float* pts, int n_sets, const int64_t* offsets, float thr, int rounds, sift_hip_homography* models,
+                                uint8_t* inlier) {
+    refine_models(pts, n_sets, offsets, thr, rounds, models, inlier);
+}
+// hostmath_ransac_homography followed by `refine` rounds on every winner; refine 0 is hostmath_ransac_homography itself
+void hostmath_ransac_homography_refined(const float* pts, int n_sets, const int64_t* offsets, uint32_t iterations, uint32_t seed, float thr,
+                                        sift_hip_homography* models, uint8_t* inlier, int32_t* scores, int refine) {
+    hostmath_ransac_homography(pts, n_sets, offsets, iterations, seed, thr, models, inlier, scores);
+    if (refine > 0) refine_models(pts, n_sets, offsets, thr, refine, models, inlier);
+}
+// The sums of one round over m rows under h: out[0 .. 5] the moments, out[6 .. 27] the normal sums.  Returns n, the number of
+// inliers, or -1 - n when n < 4 or the normalisation fails (out[6 ..] is then untouched).
+int hostmath_refine_sums(const float* pts, long long m, const float* h, float thr, double* out) {
+    float hh[9];
+    for (int k = 0; k < 9; ++k) hh[k] = h[k];
+    double mom[kRefineMoments], s[kRefineSums];
+    RefineNorm nm;
+    const int n = refine_moments(pts, m, hh, thr * thr, mom);
+    for (int k = 0; k < kRefineMoments; ++k) out[k] = mom[k];
+    if (n < 4 || !refine_normalisation(mom, n, nm)) return -1 - n;
+    refine_normal_sums(pts, m, hh, thr * thr, nm, s);
+    for (int k = 0; k < kRefineSums; ++k) out[kRefineMoments + k] = s[k];
+    return n;
+}
+// the centroids and scales of hostmath_refine_sums' normalisation: cqx, cqy, sq, ctx, cty, st; returns 1 when it exists
+int hostmath_refine_normalisation(const double* mom, int n, double* out) {
+    double mm[kRefineMoments];
+    for (int k = 0; k < kRefineMoments; ++k) mm[k] = mom[k];
+    RefineNorm nm;
+    const bool ok = refine_normalisation(mm, n, nm);
+    out[0] = nm.cqx; out[1] = nm.cqy; out[2] = nm.sq; out[3] = nm.ctx; out[4] = nm.cty; out[5] = nm.st;
+    return ok ? 1 : 0;
+}
+// a: 8 x 8 row-major, b: 8 -> x: 8; returns 1 when the elimination finds eight pivots and a finite solution
+int hostmath_solve8(const double* a, const double* b, double* x) {
+    double M[72], xx[8] = {};
+    for (int i = 0; i < 8; ++i) {
+        for (int j = 0; j < 8; ++j) M[9 * i + j] = a[8 * i + j];
+        M[9 * i + 8] = b[i];
+    }
+    const bool ok = refine_solve8(M, xx);
+    for (int i = 0; i < 8; ++i) x[i] = xx[i];
+    return ok ? 1 : 0;
 }
 }

@@ -10,6 +10,7 @@
 // short lists (a few hundred rows) that a ratio test leaves; this one wastes lanes only below 256 iterations.
 #include "ransac_kernels.h"
 #include "ransac_math.h"
+#include "ransac_refine_math.h"
 
 namespace sift_hip {
 
@@ -102,7 +103,156 @@ __global__ __launch_bounds__(256) void ransac_select_kernel(const RansacHyp* __r
     if (tid < 9) out->h[tid] = any ? hyp[base + win].h[tid] : 0.0f;
     if (tid == 9) out->inliers = any ? s_score[0] : 0;
     if (tid == 10) out->iteration = any ? win : -1;
-    if (tid == 11) out->reserved = 0;
+    if (tid == 11) out->refined = 0;
+}
+
+namespace {
+// The wave's part of a fixed-order sum: the xor butterfly w = 1 .. 32.  Lane p holds s[p] + s[p ^ w], which is bit for bit the
+// adjacent tree's s[p & ~w] + s[p | w]; after the last step every lane of the wave holds the sum of the wave's 64 partials.
+__device__ __forceinline__ double refine_wave_sum(double v) {
+#pragma unroll
+    for (int w = 1; w < 64; w <<= 1) v = v + __shfl_xor(v, w, 64);
+    return v;
+}
+__device__ __forceinline__ int refine_wave_count(int v) {
+#pragma unroll
+    for (int w = 1; w < 64; w <<= 1) v += __shfl_xor(v, w, 64);
+    return v;
+}
+}  // namespace
+
+// One workgroup of kRefineLanes lanes per set, every round of the set in this one launch (ransac_refine_math.h).  Lane p owns
+// partial p of every fixed-order sum, in registers; the four waves' sums meet in LDS as (W0 + W1) + (W2 + W3).  Whatever
+// decides how a round ends (n, the normalisation, the pivots, the solution, c') is computed by EVERY lane from the same LDS
+// values, so the decision is uniform by construction: all lanes leave the loop together, and none before the last barrier it
+// shares.  The 8 x 9 system lives in LDS: lane 9 i + j (< 72) updates entry (i, j) of an elimination step.
+// The score c of the model a round starts from is the n of its first pass, so the caller's models (sift_hip_refine_homography)
+// need none; rounds == 0 only counts.
+__global__ __launch_bounds__(kRefineLanes) void ransac_refine_kernel(const float* __restrict__ pts, const int64_t* __restrict__ off, int rounds,
+                                                                     float thr2, sift_hip_homography* __restrict__ models) {
+    __shared__ double s_part[kRefineSums * 4];   // the waves' sums of a pass
+    __shared__ double s_M[72];                   // the augmented normal equations
+    __shared__ int s_cnt[4];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    sift_hip_homography* mdl = models + blockIdx.x;
+    if (mdl->iteration < 0) return;   // none: left alone.  The whole workgroup, before any barrier.
+    const int64_t row0 = off[blockIdx.x];
+    const int m = (int)(off[blockIdx.x + 1] - row0);
+    const f4v* __restrict__ rows = reinterpret_cast<const f4v*>(pts + 4 * row0);
+    float h[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) h[k] = mdl->h[k];
+    int c = 0, refined = 0;
+    for (int round = 0; round < (rounds > 0 ? rounds : 1); ++round) {
+        __syncthreads();   // the LDS of the previous round is read
+        // ---- pass 1: the inliers of h and their moments ----
+        int n = 0;
+        double mom[kRefineMoments];
+#pragma unroll
+        for (int k = 0; k < kRefineMoments; ++k) mom[k] = 0.0;
+        for (int i = tid; i < m; i += kRefineLanes) {
+            const f4v r = rows[i];
+            const bool in = ransac_inlier(h, r.x, r.y, r.z, r.w, thr2);
+            double t[kRefineMoments];
+            refine_moment_terms(r.x, r.y, r.z, r.w, t);
+            n += in ? 1 : 0;
+#pragma unroll
+            for (int k = 0; k < kRefineMoments; ++k) mom[k] = in ? mom[k] + t[k] : mom[k];
+        }
+        n = refine_wave_count(n);
+#pragma unroll
+        for (int k = 0; k < kRefineMoments; ++k) mom[k] = refine_wave_sum(mom[k]);
+        if ((tid & 63) == 0) {
+            s_cnt[wave] = n;
+#pragma unroll
+            for (int k = 0; k < kRefineMoments; ++k) s_part[4 * k + wave] = mom[k];
+        }
+        __syncthreads();
+        n = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+#pragma unroll
+        for (int k = 0; k < kRefineMoments; ++k) mom[k] = (s_part[4 * k] + s_part[4 * k + 1]) + (s_part[4 * k + 2] + s_part[4 * k + 3]);
+        c = n;   // the score of h is its inlier count
+        if (rounds == 0) break;
+        RefineNorm nm;
+        if (n < 4 || !refine_normalisation(mom, n, nm)) break;
+        __syncthreads();   // s_part is read
+        // ---- pass 2: the normal sums ----
+        {
+            double acc[kRefineSums];
+#pragma unroll
+            for (int k = 0; k < kRefineSums; ++k) acc[k] = 0.0;
+            for (int i = tid; i < m; i += kRefineLanes) {
+                const f4v r = rows[i];
+                const bool in = ransac_inlier(h, r.x, r.y, r.z, r.w, thr2);
+                double t[kRefineSums];
+                refine_normal_terms(nm, r.x, r.y, r.z, r.w, t);
+#pragma unroll
+                for (int k = 0; k < kRefineSums; ++k) acc[k] = in ? acc[k] + t[k] : acc[k];
+            }
+#pragma unroll
+            for (int k = 0; k < kRefineSums; ++k) acc[k] = refine_wave_sum(acc[k]);
+            if ((tid & 63) == 0) {
+#pragma unroll
+                for (int k = 0; k < kRefineSums; ++k) s_part[4 * k + wave] = acc[k];
+            }
+            __syncthreads();
+            if (tid == 0) {
+#pragma unroll
+                for (int k = 0; k < kRefineSums; ++k) acc[k] = (s_part[4 * k] + s_part[4 * k + 1]) + (s_part[4 * k + 2] + s_part[4 * k + 3]);
+                refine_system(acc, n, s_M);
+            }
+            __syncthreads();
+        }
+        // ---- the solve: step k reads its inputs, a barrier, writes, a barrier ----
+        bool ok = true;
+        const int ei = tid / 9, ej = tid - 9 * ei;   // this lane's entry, for tid < 72
+        for (int k = 0; k < 8; ++k) {
+            bool piv_ok;
+            const int p = refine_pivot(s_M, k, piv_ok);
+            ok &= piv_ok;
+            double val = 0.0, pj = 0.0, f = 0.0;
+            const bool mine = tid < 72 && ei >= k;
+            int src = ei;
+            if (mine) {
+                src = ei == k ? p : (ei == p ? k : ei);   // rows k and p change places
+                val = s_M[9 * src + ej];
+                pj = s_M[9 * p + ej];
+                f = s_M[9 * src + k] / s_M[9 * p + k];
+            }
+            __syncthreads();
+            if (mine) s_M[9 * ei + ej] = (ei > k && ej > k) ? refine_eliminate(f, pj, val) : val;
+            __syncthreads();
+        }
+        double x[8];
+        ok &= refine_backsubstitute(s_M, x);
+        float h2[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) h2[k] = h[k];
+        ok = ok && refine_denormalise(x, nm, h2);
+        if (!ok) break;
+        // ---- pass 3: the score of the new model ----
+        int c2 = 0;
+        for (int i = tid; i < m; i += kRefineLanes) {
+            const f4v r = rows[i];
+            c2 += ransac_inlier(h2, r.x, r.y, r.z, r.w, thr2) ? 1 : 0;
+        }
+        c2 = refine_wave_count(c2);
+        if ((tid & 63) == 0) s_cnt[wave] = c2;
+        __syncthreads();
+        c2 = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+        if (c2 < c) break;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) h[k] = h2[k];
+        ++refined;
+        c = c2;
+        if (c2 == n) break;
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) mdl->h[k] = h[k];
+        mdl->inliers = c;
+        mdl->refined = refined;
+    }
 }
 
 // one lane per row: the predicate under the winner of the row's set
@@ -154,6 +304,10 @@ void launch_ransac_score(hipStream_t s, const float* d_pts, const RansacHyp* d_h
 void launch_ransac_select(hipStream_t s, const RansacHyp* d_hyp, int n_sets, uint32_t iterations, int32_t* d_scores, sift_hip_homography* d_models) {
     if (n_sets <= 0) return;
     hipLaunchKernelGGL(ransac_select_kernel, dim3((unsigned)n_sets), dim3(256), 0, s, d_hyp, iterations, d_scores, d_models);
+}
+void launch_ransac_refine(hipStream_t s, const float* d_pts, const int64_t* d_off, int n_sets, int rounds, float thr2, sift_hip_homography* d_models) {
+    if (n_sets <= 0) return;
+    hipLaunchKernelGGL(ransac_refine_kernel, dim3((unsigned)n_sets), dim3(kRefineLanes), 0, s, d_pts, d_off, rounds, thr2, d_models);
 }
 void launch_ransac_flags(hipStream_t s, const float* d_pts, const int64_t* d_off, int n_sets, long long rows, const sift_hip_homography* d_models,
                          float thr2, uint8_t* d_inlier) {

@@ -43,6 +43,7 @@ int check_params(const sift_hip_ransac_params* p, char* err, int errlen) {
     if (!p) return fail(err, errlen, "sift_hip ransac: no parameters");
     if (p->iterations < 1 || p->iterations > 65536) return fail(err, errlen, "sift_hip ransac: iterations must be 1 .. 65536");
     if (!(std::isfinite(p->threshold) && p->threshold > 0.0f)) return fail(err, errlen, "sift_hip ransac: threshold must be finite and > 0");
+    if (p->refine > 8) return fail(err, errlen, "sift_hip ransac: refine must be 0 .. 8");
     return SIFT_HIP_OK;
 }
 
@@ -66,6 +67,9 @@ struct Job {
     int32_t* scores;
     char* err;
     int errlen;
+    bool refine_only = false;   // sift_hip_refine_homography: `models` are the caller's, no sampling; params is null
+    float threshold = 0.0f;     //   its threshold and rounds
+    int rounds = 0;
 };
 
 int run(void* arg) {
@@ -74,7 +78,12 @@ int run(void* arg) {
     SIFT_HIP_CHECK(hipSetDevice(v.device));
 
     // ---- arguments ----
-    if (const int rc = check_params(j.params, j.err, j.errlen)) return rc;
+    if (j.refine_only) {
+        if (!(std::isfinite(j.threshold) && j.threshold > 0.0f)) return fail(j.err, j.errlen, "sift_hip ransac: threshold must be finite and > 0");
+        if (j.rounds < 0 || j.rounds > 8) return fail(j.err, j.errlen, "sift_hip ransac: rounds must be 0 .. 8");
+    } else if (const int rc = check_params(j.params, j.err, j.errlen)) {
+        return rc;
+    }
     if (j.n_sets < 0 || (j.n_sets > 0 && (!j.offsets || !j.models))) return fail(j.err, j.errlen, "sift_hip ransac: bad set arguments");
     if (j.n_sets == 0) return SIFT_HIP_OK;
     if (j.offsets[0] < 0) return fail(j.err, j.errlen, "sift_hip ransac: offsets must start at >= 0");
@@ -83,23 +92,24 @@ int run(void* arg) {
     const long long rows = (long long)j.offsets[j.n_sets];
     if (rows > 0x7fffffffLL / 4) return fail(j.err, j.errlen, "sift_hip ransac: too many rows");
     if (rows > 0 && !j.pts && !j.gather) return fail(j.err, j.errlen, "sift_hip ransac: no rows");
-    const uint32_t iters = j.params->iterations;
+    const uint32_t iters = j.refine_only ? 0u : j.params->iterations;
     const long long n_hyp = (long long)j.n_sets * iters;
     if (n_hyp > 0x7fffffffLL / 2) return fail(j.err, j.errlen, "sift_hip ransac: too many hypotheses (sets x iterations)");
-    const float thr2 = j.params->threshold * j.params->threshold;
+    const float thr = j.refine_only ? j.threshold : j.params->threshold, thr2 = thr * thr;
+    const int rounds = j.refine_only ? j.rounds : (int)j.params->refine;
 
     // ---- the tile table: every set's hypothesis blocks against every range of its rows ----
     std::vector<RansacTile> tiles;
     long long n_tiles = 0;
     for (int s = 0; s < j.n_sets; ++s) {
         const long long m = j.offsets[s + 1] - j.offsets[s];
-        if (m >= 4) n_tiles += ((iters + kRansacHyps - 1) / kRansacHyps) * ((m + kRansacRows - 1) / kRansacRows);
+        if (m >= 4 && !j.refine_only) n_tiles += ((iters + kRansacHyps - 1) / kRansacHyps) * ((m + kRansacRows - 1) / kRansacRows);
     }
     if (n_tiles > 0x7fffffffLL / 16) return fail(j.err, j.errlen, "sift_hip ransac: too many tiles");
     tiles.reserve((size_t)n_tiles);
     for (int s = 0; s < j.n_sets; ++s) {
         const long long r0 = j.offsets[s], m = j.offsets[s + 1] - r0;
-        if (m < 4) continue;   // no hypothesis of such a set is valid
+        if (m < 4 || j.refine_only) continue;   // no hypothesis of such a set is valid
         for (long long lo = 0; lo < m; lo += kRansacRows)
             for (uint32_t h0 = 0; h0 < iters; h0 += kRansacHyps)
                 tiles.push_back(RansacTile{s, (int)h0, (int)(r0 + lo), (int)(r0 + std::min<long long>(m, lo + kRansacRows))});
@@ -149,8 +159,8 @@ int run(void* arg) {
     // ---- results: written in place when the caller's array is device memory ----
     const bool models_direct = match_ptr_on_device(j.models), inlier_direct = j.inlier && match_ptr_on_device(j.inlier),
                scores_direct = j.scores && match_ptr_on_device(j.scores);
-    st.d_hyp.ensure((size_t)n_hyp * sizeof(RansacHyp));
-    if (!scores_direct) st.d_scores.ensure((size_t)n_hyp * sizeof(int32_t));
+    st.d_hyp.ensure((size_t)std::max<long long>(n_hyp, 1) * sizeof(RansacHyp));
+    if (!scores_direct) st.d_scores.ensure((size_t)std::max<long long>(n_hyp, 1) * sizeof(int32_t));
     if (!models_direct) st.d_models.ensure((size_t)j.n_sets * sizeof(sift_hip_homography));
     if (j.inlier && !inlier_direct) st.d_inlier.ensure((size_t)std::max<long long>(rows, 1));
     int32_t* d_scores = scores_direct ? j.scores : st.d_scores.as<int32_t>();
@@ -161,10 +171,19 @@ int run(void* arg) {
     if (j.gather)
         launch_ransac_gather(v.stream, j.gather->d_recs, st.d_off.as<int64_t>(), j.n_sets, rows, j.gather->d_kp, st.d_kp_row0.as<int>(),
                              j.gather->coord_scale, st.d_pts.as<float>());
-    SIFT_HIP_CHECK(hipMemsetAsync(d_scores, 0, (size_t)n_hyp * sizeof(int32_t), v.stream));
-    launch_ransac_hypotheses(v.stream, d_pts, st.d_off.as<int64_t>(), j.n_sets, iters, j.params->seed, st.d_hyp.as<RansacHyp>());
-    launch_ransac_score(v.stream, d_pts, st.d_hyp.as<RansacHyp>(), st.d_tiles.as<RansacTile>(), (int)tiles.size(), iters, thr2, d_scores);
-    launch_ransac_select(v.stream, st.d_hyp.as<RansacHyp>(), j.n_sets, iters, d_scores, d_models);
+    if (j.refine_only) {
+        if (!models_direct) {
+            match_upload(j.c, d_models, j.models, (size_t)j.n_sets * sizeof(sift_hip_homography));
+            match_wait(j.c);
+        }
+    } else {
+        SIFT_HIP_CHECK(hipMemsetAsync(d_scores, 0, (size_t)n_hyp * sizeof(int32_t), v.stream));
+        launch_ransac_hypotheses(v.stream, d_pts, st.d_off.as<int64_t>(), j.n_sets, iters, j.params->seed, st.d_hyp.as<RansacHyp>());
+        launch_ransac_score(v.stream, d_pts, st.d_hyp.as<RansacHyp>(), st.d_tiles.as<RansacTile>(), (int)tiles.size(), iters, thr2, d_scores);
+        launch_ransac_select(v.stream, st.d_hyp.as<RansacHyp>(), j.n_sets, iters, d_scores, d_models);
+    }
+    // every round of every set in one launch; with refine 0 the models are the selection's
+    if (j.refine_only || rounds > 0) launch_ransac_refine(v.stream, d_pts, st.d_off.as<int64_t>(), j.n_sets, rounds, thr2, d_models);
     if (j.inlier) launch_ransac_flags(v.stream, d_pts, st.d_off.as<int64_t>(), j.n_sets, rows, d_models, thr2, d_inlier);
     SIFT_HIP_CHECK(hipGetLastError());
 
@@ -186,6 +205,16 @@ int sift_hip_ransac_homography(sift_hip_ctx* c, const float* pts, int n_sets, co
                                sift_hip_homography* models, uint8_t* inlier, int32_t* scores, char* err, int errlen) {
     if (!c) { match_set_err(err, errlen, "sift_hip_ransac_homography: no context (the verification runs on the GPU only)"); return SIFT_HIP_EINVAL; }
     Job j{c, pts, nullptr, n_sets, offsets, params, models, inlier, scores, err, errlen};
+    return match_guarded(err, errlen, run, &j);
+}
+
+int sift_hip_refine_homography(sift_hip_ctx* c, const float* pts, int n_sets, const int64_t* offsets, float threshold, int rounds,
+                               sift_hip_homography* models, uint8_t* inlier, char* err, int errlen) {
+    if (!c) { match_set_err(err, errlen, "sift_hip_refine_homography: no context (the refinement runs on the GPU only)"); return SIFT_HIP_EINVAL; }
+    Job j{c, pts, nullptr, n_sets, offsets, nullptr, models, inlier, nullptr, err, errlen};
+    j.refine_only = true;
+    j.threshold = threshold;
+    j.rounds = rounds;
     return match_guarded(err, errlen, run, &j);
 }
 

@@ -1,5 +1,5 @@
 // RANSAC homography: the records the host (ransac.cpp) hands to the kernels (kernels_ransac.hip), their launchers, and what
-// ransac.cpp needs from a context and from the matcher.  The definition of the result is ransac_math.h.
+// ransac.cpp needs from a context and from the matcher.  The definition of the result is ransac_math.h and ransac_refine_math.h.
 #pragma once
 #include <stdint.h>
 
@@ -26,6 +26,8 @@ void launch_ransac_score(hipStream_t s, const float* d_pts, const RansacHyp* d_h
                          float thr2, int32_t* d_scores);
 // invalid hypotheses' scores become -1; the winner of every set -> d_models
 void launch_ransac_select(hipStream_t s, const RansacHyp* d_hyp, int n_sets, uint32_t iterations, int32_t* d_scores, sift_hip_homography* d_models);
+// `rounds` refinement rounds (ransac_refine_math.h) on every model with iteration >= 0, in place: h, inliers, refined
+void launch_ransac_refine(hipStream_t s, const float* d_pts, const int64_t* d_off, int n_sets, int rounds, float thr2, sift_hip_homography* d_models);
 void launch_ransac_flags(hipStream_t s, const float* d_pts, const int64_t* d_off, int n_sets, long long rows, const sift_hip_homography* d_models,
                          float thr2, uint8_t* d_inlier);
 // rows of sift_hip_result_verify: record i of pair p (d_off: the pairs' record offsets) -> (qx, qy, tx, ty); d_kp_row0: for

@@ -12,8 +12,8 @@
 //              the highest score, the lowest iteration among equals; none (iteration -1, inliers 0, h all +0.0f, every flag 0)
 //              when no hypothesis is valid or the set has fewer than four rows.  The flags are the predicate under the winner.
 // Scores are integers: the result cannot depend on how rows or hypotheses are tiled, split over workgroups or reduced.
-// The returned H is the best MINIMAL-SAMPLE model: there is no least-squares refit over the inliers (its sums would need a fixed
-// order to stay bit-defined), no adaptive early stop, no other model.
+// The H these functions select is the best MINIMAL-SAMPLE model; its least-squares refit over the inliers, with sums in a fixed
+// order so that it stays bit-defined, is ransac_refine_math.h.  There is no adaptive early stop and no other model.
 #pragma once
 #include <stdint.h>
 

@@ -447,10 +447,11 @@ class Context:
 
     # ---- geometric verification (include/sift_hip.h, "geometric verification") ----------------------------
     def ransac_homography(self, pts, offsets=None, iterations=2048, threshold=3.0, seed=0, want_scores=False, models_out=None,
-                          inlier_out=None, scores_out=None):
+                          inlier_out=None, scores_out=None, refine=0):
         """sift_hip_ransac_homography: the best four-point homography of every set of correspondences (qx, qy, tx, ty) ->
-        (models, inlier[, scores]): models[s] = (h [9] row-major, inliers, iteration; -1: none), inlier one byte per row, scores
-        [n_sets, iterations] with `want_scores`.  `pts`: a numpy array [rows, 4], a tensor or an address (host or device memory);
+        (models, inlier[, scores]): models[s] = (h [9] row-major, inliers, iteration; -1: none, refined), inlier one byte per row,
+        scores [n_sets, iterations] with `want_scores`.  `refine`: rounds of least-squares re-estimation over the winner's inliers,
+        0 .. 8 (0: the minimal-sample model); models[s]["refined"] of them were accepted.  `pts`: a numpy array [rows, 4], a tensor or an address (host or device memory);
         `offsets`: n_sets + 1 row offsets (None: one set, numpy input only); `*_out`: where a result goes instead of a new numpy
         array (returned as given)."""
         if isinstance(pts, np.ndarray):
@@ -465,7 +466,7 @@ class Context:
         scores = scores_out
         if scores is None and want_scores:
             scores = np.zeros((n_sets, int(iterations) if 0 < iterations <= 65536 else 0), np.int32)   # out of range: the call says so
-        prm = _lib.RansacParams(int(iterations) & 0xffffffff, int(seed) & 0xffffffff, float(threshold), 0)
+        prm = _lib.RansacParams(int(iterations) & 0xffffffff, int(seed) & 0xffffffff, float(threshold), int(refine) & 0xffffffff)
         err = C.create_string_buffer(512)
         rc = self._L.sift_hip_ransac_homography(self._h, self._addr(pts), n_sets, offsets, C.byref(prm), self._addr(models), self._addr(inlier),
                                                 self._addr(scores), err, 512)
@@ -473,9 +474,33 @@ class Context:
             _raise(rc, err)
         return (models, inlier, scores) if scores is not None else (models, inlier)
 
-    def verify_images(self, pairs, ratio=0.8, cross_check=False, iterations=2048, threshold=3.0, seed=0):
+    def refine_homography(self, pts, models, offsets=None, threshold=3.0, rounds=2, inlier_out=None):
+        """sift_hip_refine_homography: at most `rounds` (0 .. 8) rounds of least-squares re-estimation of given models over their
+        own inliers, no sampling -> (models, inlier).  `models`: a HOMOGRAPHY_DTYPE array (copied; h and iteration are read, a
+        model with iteration -1 is left alone), or a tensor / address that is refined in place and returned as given."""
+        if isinstance(pts, np.ndarray):
+            pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 4)
+        if offsets is None:
+            offsets = [0, pts.shape[0]]
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        n_sets = max(offsets.size - 1, 0)
+        rows = int(offsets[-1]) if offsets.size and offsets[-1] > 0 else 0
+        if isinstance(models, np.ndarray):
+            models = np.array(models, _lib.HOMOGRAPHY_DTYPE).reshape(-1)
+            if models.size != n_sets:
+                raise ValueError("refine_homography: one model per set")
+        inlier = np.zeros(rows, np.uint8) if inlier_out is None else inlier_out
+        err = C.create_string_buffer(512)
+        rc = self._L.sift_hip_refine_homography(self._h, self._addr(pts), n_sets, offsets, float(threshold), int(rounds), self._addr(models),
+                                                self._addr(inlier), err, 512)
+        if rc:
+            _raise(rc, err)
+        return models, inlier
+
+    def verify_images(self, pairs, ratio=0.8, cross_check=False, iterations=2048, threshold=3.0, seed=0, refine=0):
         """sift_hip_result_verify: match_images followed by ransac_homography on the matches' image coordinates, all on the
-        device-resident results -> (records, counts, models, inlier): models[p] belongs to pair p, inlier[i] to records[i]."""
+        device-resident results -> (records, counts, models, inlier): models[p] belongs to pair p, inlier[i] to records[i].
+        `refine` as for ransac_homography."""
         pq, pt = self._pairs(pairs)
         cnt = self.counts() if self._L.sift_hip_result_images(self._h) >= 0 else np.zeros(0, np.int32)   # none: the call says so
         rows = int(sum(cnt[q] for q in pq if 0 <= q < cnt.size))
@@ -485,7 +510,7 @@ class Context:
         counts = np.zeros(pq.size, np.int32)
         total = C.c_int64()
         mprm = _lib.MatchParams(float(ratio), 1 if cross_check else 0)
-        rprm = _lib.RansacParams(int(iterations) & 0xffffffff, int(seed) & 0xffffffff, float(threshold), 0)
+        rprm = _lib.RansacParams(int(iterations) & 0xffffffff, int(seed) & 0xffffffff, float(threshold), int(refine) & 0xffffffff)
         err = C.create_string_buffer(512)
         rc = self._L.sift_hip_result_verify(self._h, pq.size, pq, pt, C.byref(mprm), C.byref(rprm), C.c_void_p(recs.ctypes.data), counts,
                                             C.byref(total), C.c_void_p(models.ctypes.data), C.c_void_p(inlier.ctypes.data), err, 512)
@@ -678,10 +703,11 @@ class Sift:
         return self.ctx.match(qa, qb, ratio, cross_check, ka, kb)
 
     def verify(self, points_a, points_b, ratio: float = 0.8, cross_check: bool = False, iterations: int = 2048, threshold: float = 3.0,
-               seed: int = 0):
+               seed: int = 0, refine: int = 0):
         """match() followed by the geometric check of its list (an extension) -> (records, model, inlier): the best four-point
         homography from image a to image b over the matches' image coordinates (loc * 2^octave, halved with subpixel), as one
-        record (h [9] row-major, inliers, iteration; -1: none), and one flag per record."""
+        record (h [9] row-major, inliers, iteration; -1: none, refined), and one flag per record.  `refine`: rounds of
+        least-squares re-estimation over the inliers, 0 .. 8 (0: the minimal-sample model)."""
         recs = self.match(points_a, points_b, ratio, cross_check)
         scale = np.float32(0.5 if self.subpixel else 1.0)
 
@@ -689,5 +715,5 @@ class Sift:
             xy = np.array([[points[i].loc[0] << points[i].octave, points[i].loc[1] << points[i].octave] for i in which], np.float32)
             return xy.reshape(-1, 2) * scale
         pts = np.concatenate([coords(points_a, recs["query"]), coords(points_b, recs["train"])], axis=1)
-        models, inlier = self.ctx.ransac_homography(pts, None, iterations, threshold, seed)
+        models, inlier = self.ctx.ransac_homography(pts, None, iterations, threshold, seed, refine=refine)
         return recs, models[0], inlier

@@ -13,7 +13,14 @@ Timing: a warm-up, then --reps repetitions of each arm in turn; median and min -
 library's calls return when the result is in place; the torch arm ends in a synchronize).  predicates/s = sets' rows x
 iterations / time (invalid hypotheses are not scored, so the work done is smaller: "valid_share").
 
+The refine arm (--refine-arm) runs the RANSAC-alone cases (a), (b) and (c) with `refine` 0 and `refine` 2 alternating in one run -
+the difference of the medians is what the refinement stage (one more launch, ransac_refine_kernel) adds to a call - compares the
+refined models and flags bit for bit with the host loop (hostmath_ransac_homography_refined), and records the corner error of
+the minimal-sample and the refined model on the synthetic case of tests/test_refine_host.py (600 rows, 60 % outliers, 0.5 px
+noise, 512 hypotheses, seeds 0 .. 19, `refine` 8).  It APPENDS its lines to --out.
+
     python tools/ransac_bench.py [--reps 20] [--frames 32] [--out profiles/ransac_bench.txt]
+    python tools/ransac_bench.py --refine-arm [--reps 20] [--out profiles/ransac_bench.txt]
 """
 import argparse
 import json
@@ -40,10 +47,12 @@ def main():
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--iterations", type=int, default=2048)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--refine-arm", action="store_true", help="only the refine arm: refine 0 against refine 2, appended to --out")
     args = ap.parse_args()
 
     import torch
     import ransac_ref as R
+    import refine_ref as F
     from sift_amd import _lib
     from sift_amd.sift import Context, K_SQRT2
     from sift_amd.synthetic import synth_batch
@@ -118,6 +127,30 @@ def main():
               "speedup_vs_torch": round(t["median_ms"] / f["median_ms"], 2), "speedup_vs_host_loop": round(host["median_ms"] / f["median_ms"], 1),
               **extra})
 
+    def refine_case(name, ctx, pts, off, rounds=2):
+        """The same call with refine 0 and with refine `rounds`, alternating; rows and results resident on the device."""
+        n_sets = off.size - 1
+        dpts = torch.from_numpy(pts).cuda()
+        dm = torch.zeros((n_sets, 12), dtype=torch.int32, device="cuda")
+        df = torch.zeros((max(pts.shape[0], 1),), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        plain, fine = race(lambda: ctx.ransac_homography(dpts, off, its, thr, 0, models_out=dm, inlier_out=df),
+                           lambda: ctx.ransac_homography(dpts, off, its, thr, 0, models_out=dm, inlier_out=df, refine=rounds))
+        want = F.ransac(pts, off, its, thr, 0, refine=rounds)
+        base = R.ransac(pts, off, its, thr, 0)
+        ok = dm.cpu().numpy().tobytes() == want[0].tobytes() and df.cpu().numpy()[:pts.shape[0]].tobytes() == want[1].tobytes()
+        emit({"case": "refine arm, " + name, "sets": int(n_sets), "rows": int(pts.shape[0]), "iterations": its, "refine": rounds,
+              "bitwise_equal_to_host_loop": bool(ok), "refine_0": plain, f"refine_{rounds}": fine,
+              "added_ms_median": round(fine["median_ms"] - plain["median_ms"], 4), "rounds_accepted": want[0]["refined"].tolist()[:8],
+              "inliers_minimal": base[0]["inliers"].tolist()[:8], "inliers_refined": want[0]["inliers"].tolist()[:8]})
+
+    def finish(mode, header):
+        if args.out:
+            with open(args.out, mode) as f:
+                for h in header:
+                    f.write(h)
+                f.write("\n".join(lines) + "\n")
+
     ctx = Context(0)
     n = args.frames
     ctx.calculate_batch(synth_batch(n, 1920, 1080), _lib.Params(3, 4, 1.6, K_SQRT2, 0))
@@ -128,6 +161,34 @@ def main():
     # ---- (a): two 1080p frames' match list ----
     rec, counts = ctx.match_images([(0, 1)], 0.8, False)
     pts = np.concatenate([coords(kp, row0[0], rec["query"]), coords(kp, row0[1], rec["train"])], axis=1)
+    if args.refine_arm:
+        refine_case("a: match list of frames 1 and 2 of the bench batch", ctx, pts, np.array([0, pts.shape[0]], np.int64))
+        pairs = [(i, i + 1) for i in range(n - 1)]
+        rec, counts = ctx.match_images(pairs, 0.8, False)
+        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        pts = np.zeros((rec.size, 4), np.float32)
+        for p, (a, b) in enumerate(pairs):
+            r = rec[off[p]:off[p + 1]]
+            pts[off[p]:off[p + 1]] = np.concatenate([coords(kp, row0[a], r["query"]), coords(kp, row0[b], r["train"])], axis=1)
+        refine_case(f"b: the {len(pairs)} lists of consecutive pairs as the sets of one call", ctx, pts, off)
+        rows, _ = R.projective_rows(np.random.default_rng(0), 20000)
+        refine_case("c: 20 000 synthetic correspondences (60 % outliers)", ctx, rows, np.array([0, 20000], np.int64))
+        e0, e1, ok = [], [], True
+        for seed in range(20):
+            rows, _ = R.projective_rows(np.random.default_rng(seed), 600, outliers=0.6, noise=0.5)
+            base = ctx.ransac_homography(rows, None, 512, thr, seed)[0][0]
+            got = ctx.ransac_homography(rows, None, 512, thr, seed, refine=8)
+            want = F.ransac(rows, None, 512, thr, seed, refine=8)
+            ok = ok and got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes()
+            e0.append(F.corner_error(base["h"]))
+            e1.append(F.corner_error(got[0][0]["h"]))
+        emit({"case": "refine arm, corner error on the 1000 px square: 600 rows, 60 % outliers, 0.5 px noise, 512 hypotheses, seeds 0 .. 19, refine 8",
+              "bitwise_equal_to_host_loop": bool(ok), "minimal_px": {"min": round(min(e0), 3), "median": round(statistics.median(e0), 3), "max": round(max(e0), 3)},
+              "refined_px": {"min": round(min(e1), 3), "median": round(statistics.median(e1), 3), "max": round(max(e1), 3)},
+              "seeds_improved": int(sum(b < a for a, b in zip(e0, e1)))})
+        ctx.close()
+        finish("a", [])
+        return
     case("a: match list of frames 1 and 2 of the bench batch (ratio 0.8), rows on the device, sift_hip_ransac_homography", ctx, pts,
          np.array([0, pts.shape[0]], np.int64), {"keypoints": [int(cnt[0]), int(cnt[1])]})
 
@@ -161,11 +222,8 @@ def main():
     rows, _ = R.projective_rows(np.random.default_rng(0), 20000)
     case("c: 20 000 synthetic correspondences (60 % outliers), rows on the device", ctx, rows, np.array([0, 20000], np.int64), {})
     ctx.close()
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("# tools/ransac_bench.py: GPU RANSAC homography against the torch scoring formulation (same GPU, alternating) and the host loop (ms on the host around each call)\n")
-            f.write("# solver: largest deviation of ransac_homography4 from numpy's float64 8x8 solution over tests/test_ransac_host.py's samples, both scaled by their largest entry: 1.16e-08\n")
-            f.write("\n".join(lines) + "\n")
+    finish("w", ["# tools/ransac_bench.py: GPU RANSAC homography against the torch scoring formulation (same GPU, alternating) and the host loop (ms on the host around each call)\n",
+                 "# solver: largest deviation of ransac_homography4 from numpy's float64 8x8 solution over tests/test_ransac_host.py's samples, both scaled by their largest entry: 1.16e-08\n"])
 
 
 if __name__ == "__main__":
