@@ -142,7 +142,12 @@ int sift_hip_calculate_batch_device_u8(sift_hip_ctx* ctx, const void* dev_imgs, 
  * call failed before it ran: a failed call never leaves an earlier batch's results readable). */
 int sift_hip_result_images(sift_hip_ctx* ctx);
 /* Per-image status of the last batch (an image that "threw" has count 0).  `cap` = entries the caller's array holds;
- * SIFT_HIP_EINVAL if that is fewer than sift_hip_result_images(). */
+ * SIFT_HIP_EINVAL if that is fewer than sift_hip_result_images().
+ * The exception of sift.cpp:184 (a keypoint whose dead 16x16 blur violates Vigra's precondition) is per image: the calculate
+ * call returns the status and the message of the FIRST such image, and the batch stays readable.  Every other image has its
+ * own results; the thrown one is an empty set in the result arrays, in the sparse lists and in sift_hip_result_match /
+ * _verify (its pairs are empty).  Its pyramid levels and the stage lists the reference had formed when it threw (candidates,
+ * after_sort1) are complete; after_orient, after_sort2 and final are empty. */
 int sift_hip_result_status(sift_hip_ctx* ctx, int32_t* status, int cap);
 /* Number of returned InterestPoints per image, and their sum. */
 int sift_hip_result_counts(sift_hip_ctx* ctx, int32_t* counts, int cap);

@@ -93,6 +93,15 @@ def test_host_glue_path(ctx, report_dir):
         compare_run(ctx, synth_frame(333, 257, 9), 3, 3, False, "host-glue path 333x257", report_dir)
 
 
+def test_host_glue_path_with_some_images_throwing(ctx):
+    """The host's implementation of "an image that threw has count 0" (cleanup2_fn / mid_host, then the host's out_base and a
+    descriptor stage of its own): the seven frames of tests/test_mixed_status_gpu.py, two of which end in the reference's
+    exception, give the same per-image status, counts and result bytes as the oracle - and so as the GPU cleanup."""
+    from test_mixed_status_gpu import check_seven_frame_batch, mixed_fixture
+    with forced(ctx, gpu_cleanup=0):
+        check_seven_frame_batch(ctx, mixed_fixture(), "host-glue path, mixed statuses")
+
+
 @pytest.mark.parametrize("option", ["gate_schedule=0", "pyramid_side=0", "dog_in_extrema=0"])
 def test_other_gate_schedules_leave_the_results_alone(ctx, option):
     """The other order of the phase gate (sift_amd/csrc/phase_gate.h: schedule 0 keeps the pyramids alone on the chip) and the

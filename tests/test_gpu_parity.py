@@ -199,6 +199,33 @@ CASES = [
 ]
 
 
+def compare_image(ctx, run, image, dogs, octaves, subpixel, name, rep):
+    """Image `image` of the batch the context holds against one oracle run of that image: the replaced image (subpixel), every
+    Gaussian and DoG level and every stage list; the stage sizes go into `rep`."""
+    if subpixel:
+        assert_bits_equal(ctx.image(image), run.image(), f"{name}: replaced image")
+    for o in range(octaves):
+        for j in range(dogs + 1):
+            assert_bits_equal(ctx.level("gaussian", o, j, image), run.level("gaussian", o, j), f"{name}: gaussian({o},{j}) img{image}")
+            assert ctx.level_scale("gaussian", o, j) == run.scale("gaussian", o, j)
+        for j in range(dogs):
+            assert_bits_equal(ctx.level("dog", o, j, image), run.level("dog", o, j), f"{name}: dog({o},{j}) img{image}")
+            assert ctx.level_scale("dog", o, j) == run.scale("dog", o, j)
+    for stage in ("candidates", "after_sort1", "after_orient", "after_sort2", "final"):
+        got = ctx.stage(stage, image)
+        want, wdesc = run.points(stage)
+        rep[stage] = int(want.size)
+        assert got.size == want.size, f"{name}: {stage}: {got.size} points vs oracle {want.size}"
+        for f in ("x", "y", "octave", "index"):
+            assert (got[f] == want[f]).all(), f"{name}: {stage}: field {f} differs at {int((got[f] != want[f]).sum())} points"
+        assert (got["scale"] == want["scale"]).all(), f"{name}: {stage}: scale differs"
+        if stage in ("candidates", "after_orient", "after_sort2", "final"):
+            assert (got["filtered"].astype(bool) == want["filtered"].astype(bool)).all(), f"{name}: {stage}: filtered flags differ"
+        if stage in ("after_orient", "after_sort2", "final"):
+            m = ~want["filtered"].astype(bool)
+            assert_bits_equal(got["orientation"][m], want["orientation"][m], f"{name}: {stage}: orientation")
+
+
 def compare_run(ctx, img, dogs, octaves, subpixel, name, report_dir, batch_of=1, sigma=1.6):
     params = _lib.Params(dogs, octaves, sigma, O.K_SQRT2, 1 if subpixel else 0)
     run = O.OracleRun(img, dogs, octaves, sigma=sigma, subpixel=subpixel)
@@ -207,28 +234,7 @@ def compare_run(ctx, img, dogs, octaves, subpixel, name, report_dir, batch_of=1,
     ctx.calculate_batch(imgs, params)
     rep = {"case": name}
     for image in sorted({0, batch_of - 1}):
-        if subpixel:
-            assert_bits_equal(ctx.image(image), run.image(), f"{name}: replaced image")
-        for o in range(octaves):
-            for j in range(dogs + 1):
-                assert_bits_equal(ctx.level("gaussian", o, j, image), run.level("gaussian", o, j), f"{name}: gaussian({o},{j}) img{image}")
-                assert ctx.level_scale("gaussian", o, j) == run.scale("gaussian", o, j)
-            for j in range(dogs):
-                assert_bits_equal(ctx.level("dog", o, j, image), run.level("dog", o, j), f"{name}: dog({o},{j}) img{image}")
-                assert ctx.level_scale("dog", o, j) == run.scale("dog", o, j)
-        for stage in ("candidates", "after_sort1", "after_orient", "after_sort2", "final"):
-            got = ctx.stage(stage, image)
-            want, wdesc = run.points(stage)
-            rep[stage] = int(want.size)
-            assert got.size == want.size, f"{name}: {stage}: {got.size} points vs oracle {want.size}"
-            for f in ("x", "y", "octave", "index"):
-                assert (got[f] == want[f]).all(), f"{name}: {stage}: field {f} differs at {int((got[f] != want[f]).sum())} points"
-            assert (got["scale"] == want["scale"]).all(), f"{name}: {stage}: scale differs"
-            if stage in ("candidates", "after_orient", "after_sort2", "final"):
-                assert (got["filtered"].astype(bool) == want["filtered"].astype(bool)).all(), f"{name}: {stage}: filtered flags differ"
-            if stage in ("after_orient", "after_sort2", "final"):
-                m = ~want["filtered"].astype(bool)
-                assert_bits_equal(got["orientation"][m], want["orientation"][m], f"{name}: {stage}: orientation")
+        compare_image(ctx, run, image, dogs, octaves, subpixel, name, rep)
     counts = ctx.counts()
     kp, desc = ctx.results()
     want, wdesc = run.points("final")
