@@ -1,8 +1,9 @@
 // Two images -> matches.txt and inliers.txt: sift::Sift::calculate() on both, sift::Matcher::match() on their points, then
-// sift::Matcher::verify(): a RANSAC homography over the matches (include/sift/match.hpp; extensions, the reference has neither).
-// inliers.txt holds the lines of matches.txt that agree with the model.
+// sift::Matcher::verify(): a RANSAC homography over the matches (include/sift/match.hpp; extensions, the reference has neither) -
+// or, with model=fundamental, sift::Matcher::verify_fundamental(): a seven-point fundamental matrix, the model for two views of a
+// general scene.  inliers.txt holds the lines of matches.txt that agree with the model.
 //   g++ -std=c++17 -pthread -Iinclude examples/sift_verify.cpp -Lsift_amd/lib -lsift_hip -Wl,-rpath,$PWD/sift_amd/lib -o sift_verify
-//   ./sift_verify a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [refine=0]
+//   ./sift_verify a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [refine=0] [model=homography|fundamental]
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -36,7 +37,7 @@ static void write_matches(const char* path, const std::vector<sift::Match>& matc
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::cerr << "usage: " << argv[0]
-                  << " a.{pgm,ppm,png,jpg} b.{...} [octaves] [dogsPerEpoch] [ratio] [crossCheck] [iterations] [threshold] [seed] [refine]\n";
+                  << " a.{pgm,ppm,png,jpg} b.{...} [octaves] [dogsPerEpoch] [ratio] [crossCheck] [iterations] [threshold] [seed] [refine] [homography|fundamental]\n";
         return 1;
     }
     const u16_t octaves = argc > 3 ? (u16_t)std::atoi(argv[3]) : 4;
@@ -47,12 +48,34 @@ int main(int argc, char** argv) {
     const float threshold = argc > 8 ? (float)std::atof(argv[8]) : 3.0f;
     const unsigned seed = argc > 9 ? (unsigned)std::atoi(argv[9]) : 0u;
     const unsigned refine = argc > 10 ? (unsigned)std::atoi(argv[10]) : 0u;   // rounds of least-squares re-estimation over the inliers
+    const std::string model_name = argc > 11 ? argv[11] : "homography";
+    if (model_name != "homography" && model_name != "fundamental") {
+        std::cerr << "model must be homography or fundamental\n";
+        return 1;
+    }
+    if (model_name == "fundamental" && refine) {
+        std::cerr << "refine is for the homography: there is no least-squares refit of the fundamental matrix\n";
+        return 1;
+    }
     try {
         sift::Sift sift(dogsPerEpoch, octaves, 1.6f, std::sqrt(2.0f), false);
         const std::vector<sift::InterestPoint> a = points_of(sift, argv[1]);
         const std::vector<sift::InterestPoint> b = points_of(sift, argv[2]);
         sift::Matcher matcher;
         const std::vector<sift::Match> matches = matcher.match(a, b, ratio, crossCheck);
+        if (model_name == "fundamental") {
+            const sift::Fundamental model = matcher.verify_fundamental(a, b, matches, iterations, threshold, seed, false);
+            write_matches("matches.txt", matches, nullptr);
+            write_matches("inliers.txt", matches, &model.inlier);
+            std::cout << a.size() << " and " << b.size() << " interest points, " << matches.size() << " matches -> matches.txt, " << model.inliers
+                      << " inliers -> inliers.txt\n";
+            if (model.iteration < 0) {
+                std::cout << "no fundamental matrix\n";
+            } else {
+                for (int r = 0; r < 3; ++r) std::printf("F %.9g %.9g %.9g\n", (double)model.f[3 * r], (double)model.f[3 * r + 1], (double)model.f[3 * r + 2]);
+            }
+            return 0;
+        }
         const sift::Homography model = matcher.verify(a, b, matches, iterations, threshold, seed, false, refine);
         write_matches("matches.txt", matches, nullptr);
         write_matches("inliers.txt", matches, &model.inlier);

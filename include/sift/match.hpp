@@ -27,6 +27,15 @@ struct Homography {
     std::vector<unsigned char> inlier;   // one flag per match handed to Matcher::verify
 };
 
+struct Fundamental {
+    f32_t f[9] = {};                     // row-major, (tx, ty, 1) F (qx, qy, 1)^T = 0 with q in the query and t in the train image: the best
+                                         // seven-point model; its entry of largest magnitude is +1
+    int inliers = 0;
+    int iteration = -1;                  // the winning sample; -1: no model (fewer than seven matches, or every sample degenerate)
+    int root = -1;                       // which real root of the winner's cubic, 0 .. 2
+    std::vector<unsigned char> inlier;   // one flag per match handed to Matcher::verify_fundamental
+};
+
 class Matcher {
 public:
     explicit Matcher(int device = 0) {
@@ -81,16 +90,7 @@ public:
     // iterations outside 1 .. 65536, a threshold that is not finite and positive, or refine above 8.
     Homography verify(const std::vector<InterestPoint>& query, const std::vector<InterestPoint>& train, const std::vector<Match>& matches,
                       unsigned iterations = 2048, f32_t threshold = 3.0f, unsigned seed = 0, bool subpixel = false, unsigned refine = 0) {
-        const f32_t scale = subpixel ? 0.5f : 1.0f;
-        _pts.resize(matches.size() * 4);
-        for (size_t i = 0; i < matches.size(); ++i) {
-            const InterestPoint& q = query.at((size_t)matches[i].query);
-            const InterestPoint& t = train.at((size_t)matches[i].train);
-            _pts[4 * i] = (f32_t)((unsigned)q.loc.x << q.octave) * scale;
-            _pts[4 * i + 1] = (f32_t)((unsigned)q.loc.y << q.octave) * scale;
-            _pts[4 * i + 2] = (f32_t)((unsigned)t.loc.x << t.octave) * scale;
-            _pts[4 * i + 3] = (f32_t)((unsigned)t.loc.y << t.octave) * scale;
-        }
+        gather(query, train, matches, subpixel);
         const int64_t offsets[2] = {0, (int64_t)matches.size()};
         sift_hip_ransac_params prm{};
         prm.iterations = iterations;
@@ -111,7 +111,48 @@ public:
         return out;
     }
 
+    // The epipolar check of a match list (include/sift_hip.h, "epipolar verification"): the best seven-point fundamental matrix
+    // over the same coordinates, by the Sampson distance, and one flag per match - for two views of a general scene, where a
+    // homography explains the matches of one plane only.  A planar scene or a camera that only rotates does not determine F:
+    // verify() is the right call there.  There is no refinement.  Throws std::invalid_argument as verify() does.
+    Fundamental verify_fundamental(const std::vector<InterestPoint>& query, const std::vector<InterestPoint>& train, const std::vector<Match>& matches,
+                                   unsigned iterations = 2048, f32_t threshold = 3.0f, unsigned seed = 0, bool subpixel = false) {
+        gather(query, train, matches, subpixel);
+        const int64_t offsets[2] = {0, (int64_t)matches.size()};
+        sift_hip_ransac_params prm{};
+        prm.iterations = iterations;
+        prm.seed = seed;
+        prm.threshold = threshold;
+        sift_hip_fundamental model{};
+        Fundamental out;
+        out.inlier.assign(matches.size(), 0);
+        char err[512] = "";
+        const int rc = sift_hip_ransac_fundamental(_ctx, _pts.data(), 1, offsets, &prm, &model, out.inlier.data(), nullptr, err, sizeof(err));
+        if (rc == SIFT_HIP_EINVAL) throw std::invalid_argument(err);
+        if (rc != SIFT_HIP_OK) throw std::runtime_error(err);
+        for (int k = 0; k < 9; ++k) out.f[k] = model.f[k];
+        out.inliers = model.inliers;
+        out.iteration = model.iteration;
+        out.root = model.root;
+        return out;
+    }
+
 private:
+    // the matches' image coordinates -> _pts, rows (qx, qy, tx, ty)
+    void gather(const std::vector<InterestPoint>& query, const std::vector<InterestPoint>& train, const std::vector<Match>& matches, bool subpixel) {
+        const f32_t scale = subpixel ? 0.5f : 1.0f;
+        _pts.resize(matches.size() * 4);
+        for (size_t i = 0; i < matches.size(); ++i) {
+            const InterestPoint& q = query.at((size_t)matches[i].query);
+            const InterestPoint& t = train.at((size_t)matches[i].train);
+            _pts[4 * i] = (f32_t)((unsigned)q.loc.x << q.octave) * scale;
+            _pts[4 * i + 1] = (f32_t)((unsigned)q.loc.y << q.octave) * scale;
+            _pts[4 * i + 2] = (f32_t)((unsigned)t.loc.x << t.octave) * scale;
+            _pts[4 * i + 3] = (f32_t)((unsigned)t.loc.y << t.octave) * scale;
+        }
+    }
+
+
     sift_hip_ctx* _ctx = nullptr;
     std::vector<float> _desc;              // both lists' rows back to back, kept between calls
     std::vector<sift_hip_keypoint> _kp;

@@ -266,7 +266,7 @@ int sift_hip_result_match(sift_hip_ctx* ctx, int n_pairs, const int32_t* pair_q,
  * finite, a pivot is zero or not finite, or an entry is not finite.  h' is accepted when c' >= c, and another round follows
  * only when c' > c: the inlier count never decreases.  Every floating-point sum over rows has a FIXED ORDER: 256 partials
  * (partial p: rows i = p mod 256, ascending, from +0.0, inliers only), combined by the adjacent pairwise tree - so the result
- * stays bit-defined.  There is no adaptive early stop and no other model. */
+ * stays bit-defined.  There is no adaptive early stop; the other model, the fundamental matrix, is the next section. */
 typedef struct sift_hip_ransac_params {
     uint32_t iterations;  /* hypotheses per set, 1 .. 65536 */
     uint32_t seed;
@@ -306,6 +306,60 @@ int sift_hip_result_verify(sift_hip_ctx* ctx, int n_pairs, const int32_t* pair_q
                            const sift_hip_match_params* match_params, const sift_hip_ransac_params* ransac_params,
                            sift_hip_match_rec* recs, int32_t* counts, int64_t* total, sift_hip_homography* models,
                            uint8_t* inlier, char* err, int errlen);
+
+/* ---- epipolar verification: RANSAC fundamental matrix over match lists (an extension) -------------------
+ * The second model, for two views of a general scene: F with (tx, ty, 1) F (qx, qy, 1)^T = 0, row-major, the same query-to-train
+ * convention as H.  Rows, sets, offsets, sift_hip_ransac_params and the memory rules are those of sift_hip_ransac_homography.
+ * The result is defined bit for bit by sift_amd/csrc/ransac_fund_math.h, which the kernels and a plain host loop
+ * (hostmath_ransac_fundamental) both compile.  In words, for a set of m rows and sample i = 0 .. iterations - 1:
+ *   sample     seven distinct rows, drawn as for the homography (same hash, same key; draws k = 0 .. 6): the first four are the
+ *              homography's sample of the same (seed, set, i, m).
+ *   solve      in double.  The 7 x 9 matrix with rows [tx qx, tx qy, tx, ty qx, ty qy, ty, qx, qy, 1], coordinates unnormalised;
+ *              seven steps of Gauss-Jordan elimination with complete pivoting and no swaps (the pivot: the first entry of
+ *              largest magnitude in row-major order among unused rows and columns, never a NaN; zero or not finite: the sample
+ *              is invalid); every other row i, used ones included, gets mul = a[i][pc] / piv, a[i][j] = fma(-mul, a[pr][j],
+ *              a[i][j]) for all nine j, the pivot row is not normalised - so two identical sample rows cancel exactly and the
+ *              sample is invalid.  The unused columns f0 < f1 give the null vectors: n1 has 1 at f0, 0 at f1, -(a[i][f0] /
+ *              a[i][pc_i]) at row i's pivot column; n2 likewise from f1.  det(l n1 + n2) = c3 l^3 + c2 l^2 + c1 l + c0 by
+ *              multilinearity (c3 = det n1, c0 = det n2, c2 and c1 the sums (d + d) + d of the mixed row determinants in the
+ *              order of the replaced row; 3 x 3 determinants by cofactors along the first row, minors fma(x, y, -(z * w)), sum
+ *              fma(r0, m0, fma(r1, m1, r2 * m2))).  A = c2 / c3, B = c1 / c3, C = c0 / c3 must be finite; M = 1 + max(|A|, |B|,
+ *              |C|); p(x) = fma(fma(fma(1, x, A), x, B), x, C), p'(x) = fma(fma(3, x, 2A), x, B).  With xv = -A / 3: if
+ *              p'(xv) < 0 the critical points x1, x2 are the results of 128 fixed bisection steps of p' on [-M, xv] and [xv, M],
+ *              and the brackets are [-M, x1], [x1, x2], [x2, M]; otherwise the one bracket is [-M, M].  A bisection keeps a
+ *              negative end n and a positive end p; a step is mid = 0.5 * (n + p), a value < 0 at mid moves n, else p; the
+ *              result is p.  Bracket k holds root k when p(x) is <= 0 at one end and >= 0 at the other; the root is 128 such
+ *              steps of p.  No square root, no libm call, no early exit, no Newton step.  F[j] = fma(root, n1[j], n2[j]), all
+ *              nine finite, divided by its first entry of largest magnitude (which becomes +1), rounded to nine floats.
+ *              Hypothesis SLOT 3 i + k is root k of sample i; an invalid slot is all +0.0f.
+ *   predicate  the Sampson distance in float, no division: a = fmaf(f0, qx, fmaf(f1, qy, f2)), b from f3 .. f5, c from
+ *              f6 .. f8; r = fmaf(tx, a, fmaf(ty, b, c)); a2 = fmaf(f0, tx, fmaf(f3, ty, f6)), b2 = fmaf(f1, tx, fmaf(f4, ty,
+ *              f7)); g = fmaf(a, a, fmaf(b, b, fmaf(a2, a2, b2 * b2))); e = r * r; inlier iff e <= (thr * thr) * g and g > 0
+ *              and e < +inf.  A NaN or an infinity anywhere in a row makes it no inlier of any model.
+ *   selection  score of a slot = inliers among ALL m rows, -1 for an invalid slot; the winner has the highest score, the lowest
+ *              slot among equals.  No valid slot, or m < 7: iteration -1, root -1, inliers 0, f all +0.0f, every flag 0.
+ * Scores are integers, so the result does not depend on tiling, splits or reduction order.  Caveats: with exactly seven rows
+ * every sample is the same seven rows; a planar scene or a pure rotation does not determine F (sift_hip_ransac_homography is
+ * the right call there); there is no oriented-epipolar test.  A least-squares refit of F is out of scope: params->refine must
+ * be 0. */
+typedef struct sift_hip_fundamental {
+    float f[9];           /* row-major */
+    int32_t inliers;      /* inliers of f = number of flags set = the score of the winner */
+    int32_t iteration;    /* the winning sample; -1: none */
+    int32_t root;         /* which real root of the winner's cubic, 0 .. 2; -1: none */
+} sift_hip_fundamental;   /* 48 bytes */
+/* Arguments as for sift_hip_ransac_homography; scores (may be NULL): n_sets x 3 * iterations int32, the score of every slot.
+ * SIFT_HIP_EINVAL for refine != 0 and for everything sift_hip_ransac_homography rejects.  One launch of each kernel for all
+ * sets; scratch memory is allocated by the first call and kept with the context. */
+int sift_hip_ransac_fundamental(sift_hip_ctx* ctx, const float* pts, int n_sets, const int64_t* offsets,
+                                const sift_hip_ransac_params* params, sift_hip_fundamental* models, uint8_t* inlier,
+                                int32_t* scores, char* err, int errlen);
+/* sift_hip_result_verify with the fundamental matrix as the model: bit for bit sift_hip_result_match plus
+ * sift_hip_ransac_fundamental on the gathered coordinates. */
+int sift_hip_result_verify_fundamental(sift_hip_ctx* ctx, int n_pairs, const int32_t* pair_q, const int32_t* pair_t,
+                                       const sift_hip_match_params* match_params, const sift_hip_ransac_params* ransac_params,
+                                       sift_hip_match_rec* recs, int32_t* counts, int64_t* total, sift_hip_fundamental* models,
+                                       uint8_t* inlier, char* err, int errlen);
 
 /* ---- inspection of the last batch (parity tests) ------------------------------------------------ */
 /* kind: 0 gaussian (levels 0..D), 1 dog (0..D-1), 2 magnitude, 3 orientation (initial gradient

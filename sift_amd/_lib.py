@@ -37,6 +37,7 @@ SYMBOLS = [
     "sift_hip_rotated_rect_points", "sift_hip_overlay_box", "sift_hip_overlay_draw",
     "sift_hip_knn2", "sift_hip_match", "sift_hip_result_match",
     "sift_hip_ransac_homography", "sift_hip_result_verify", "sift_hip_refine_homography",
+    "sift_hip_ransac_fundamental", "sift_hip_result_verify_fundamental",
 ]
 
 
@@ -59,6 +60,8 @@ class RansacParams(C.Structure):
 
 HOMOGRAPHY_DTYPE = np.dtype([("h", "<f4", (9,)), ("inliers", "<i4"), ("iteration", "<i4"), ("refined", "<i4")])
 assert HOMOGRAPHY_DTYPE.itemsize == 48
+FUNDAMENTAL_DTYPE = np.dtype([("f", "<f4", (9,)), ("inliers", "<i4"), ("iteration", "<i4"), ("root", "<i4")])
+assert FUNDAMENTAL_DTYPE.itemsize == 48
 
 KEYPOINT_DTYPE = np.dtype([("scale", "<f4"), ("orientation", "<f4"), ("x", "<u2"), ("y", "<u2"),
                            ("octave", "<u2"), ("index", "<u2"), ("filtered", "u1"),
@@ -196,5 +199,7 @@ def load():
     L.sift_hip_refine_homography.argtypes = [vp, vp, ci, i64p, C.c_float, ci, vp, vp, cs, ci]
     L.sift_hip_result_verify.argtypes = [vp, ci, i32p, i32p, C.POINTER(MatchParams), C.POINTER(RansacParams), vp, i32p, C.POINTER(C.c_int64),
                                          vp, vp, cs, ci]
+    L.sift_hip_ransac_fundamental.argtypes = L.sift_hip_ransac_homography.argtypes
+    L.sift_hip_result_verify_fundamental.argtypes = L.sift_hip_result_verify.argtypes
     _lib = L
     return L

@@ -3,7 +3,7 @@ overlay :59-76) on top of the GPU path — SURVEY.md §8(f) rows 1-3.
 
     python -m sift_amd.cli -i image.pgm [-s 1.6] [-k 1.41421354] [-o 4] [-d 3] [-p 0] [-r 1]
     python -m sift_amd.cli -i a.pgm --match b.pgm [--ratio 0.8] [--cross-check]      (an extension: matches.txt)
-    python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--iterations 2048] [--threshold 3] [--seed 0] [--refine 0]   (... and inliers.txt)
+    python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--iterations 2048] [--threshold 3] [--seed 0] [--refine 0] [--model homography|fundamental]   (... and inliers.txt)
 
 Image ingest follows Vigra's scalar import: band 0 of multi-band files, values unscaled.  PGM,
 PPM, PNG and JPEG are decoded by the library itself (sift_amd/csrc/image_io.cpp, jpeg_decode.cpp: no PIL, no OpenCV, no libjpeg).
@@ -137,9 +137,16 @@ def main(argv=None) -> int:
     ap.add_argument("--threshold", type=float, default=3.0, help="inlier threshold of --verify in pixels")
     ap.add_argument("--seed", type=int, default=0, help="seed of --verify's sampling")
     ap.add_argument("--refine", type=int, default=0, help="with --verify: rounds of least-squares re-estimation over the inliers (0 .. 8)")
+    ap.add_argument("--model", choices=("homography", "fundamental"), default="homography",
+                    help="model of --verify: a four-point homography (a plane or a rotating camera), or a seven-point fundamental matrix "
+                         "(two views of a general scene)")
     args = ap.parse_args(argv)
     if args.verify and not args.match:
         ap.error("--verify needs --match")
+    if args.model != "homography" and not args.verify:
+        ap.error("--model needs --verify")
+    if args.refine and args.model == "fundamental":
+        ap.error("--refine is for --model homography: there is no least-squares refit of the fundamental matrix")
     if args.refine and not args.verify:
         ap.error("--refine needs --verify")
     if not 0 <= args.refine <= 8:
@@ -163,7 +170,7 @@ def main(argv=None) -> int:
                 matches = sift.match(points, points2, args.ratio, args.cross_check)
             else:
                 matches, model, inlier = sift.verify(points, points2, args.ratio, args.cross_check, args.iterations, args.threshold, args.seed,
-                                                     args.refine)
+                                                     args.refine, args.model)
             write_matches("matches.txt", matches)
             print(f"{len(points2)} interest points in {args.match}, {len(matches)} matches")
             if args.verify:
@@ -171,7 +178,13 @@ def main(argv=None) -> int:
                 print(f"{int(model['inliers'])} inliers -> inliers.txt")
                 if args.refine:
                     print(f"refined {int(model['refined'])} rounds")
-                if model["iteration"] < 0:
+                if args.model == "fundamental":
+                    if model["iteration"] < 0:
+                        print("no fundamental matrix")
+                    else:
+                        for r in range(3):
+                            print("F " + " ".join("%.9g" % float(v) for v in model["f"][3 * r:3 * r + 3]))
+                elif model["iteration"] < 0:
                     print("no homography")
                 else:
                     for r in range(3):

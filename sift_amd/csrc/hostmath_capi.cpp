@@ -8,9 +8,10 @@
 #include "grad_math.h"
 #include "hist_bins.h"
 #include "linalg3.h"
+#include "ransac_fund_math.h"
 #include "ransac_math.h"
 #include "ransac_refine_math.h"
-#include "../../include/sift_hip.h"   // sift_hip_homography
+#include "../../include/sift_hip.h"   // sift_hip_homography, sift_hip_fundamental
 
 extern "C" {
 float hostmath_atan2f(float y, float x) { return sift_hip::fdlibm_atan2f(y, x); }
@@ -297,5 +298,76 @@ int hostmath_solve8(const double* a, const double* b, double* x) {
     const bool ok = refine_solve8(M, xx);
     for (int i = 0; i < 8; ++i) x[i] = xx[i];
     return ok ? 1 : 0;
+}
+}
+
+// ---- RANSAC fundamental matrix as ransac_fund_math.h defines it, in plain loops: what sift_hip_ransac_fundamental must
+// reproduce bit for bit.
+extern "C" {
+void hostmath_ransac_draw7(uint32_t seed, uint32_t set, uint32_t iteration, uint32_t m, uint32_t* idx) {
+    uint32_t d[7];
+    sift_hip::ransac_draw7(seed, set, iteration, m, d);
+    for (int k = 0; k < 7; ++k) idx[k] = d[k];
+}
+// c: seven rows (qx, qy, tx, ty); f: 3 x 9 floats; returns the mask of valid slots
+int hostmath_fundamental7(const float* c, float* f) {
+    float cc[7][4], ff[3][9];
+    for (int k = 0; k < 28; ++k) cc[k / 4][k % 4] = c[k];
+    const uint32_t mask = sift_hip::ransac_fundamental7(cc, ff);
+    for (int k = 0; k < 27; ++k) f[k] = ff[k / 9][k % 9];
+    return (int)mask;
+}
+int hostmath_fund_inlier(const float* f, const float* row, float thr) {
+    float ff[9];
+    for (int k = 0; k < 9; ++k) ff[k] = f[k];
+    return sift_hip::ransac_fund_inlier(ff, row[0], row[1], row[2], row[3], thr * thr) ? 1 : 0;
+}
+// pts, offsets, inlier as for hostmath_ransac_homography; scores (may be NULL): n_sets x 3 * iterations
+void hostmath_ransac_fundamental(const float* pts, int n_sets, const int64_t* offsets, uint32_t iterations, uint32_t seed, float thr,
+                                 sift_hip_fundamental* models, uint8_t* inlier, int32_t* scores) {
+    const float thr2 = thr * thr;
+    if (inlier && n_sets > 0)
+        for (int64_t i = 0; i < offsets[0]; ++i) inlier[i] = 0;   // rows in front of the first set belong to none
+    for (int s = 0; s < n_sets; ++s) {
+        const float* p = pts + 4 * offsets[s];
+        const int64_t m = offsets[s + 1] - offsets[s];
+        sift_hip_fundamental best{};
+        best.iteration = -1;
+        best.root = -1;
+        int32_t best_score = -1;
+        for (uint32_t it = 0; it < iterations; ++it) {
+            float f[3][9] = {};
+            uint32_t mask = 0;
+            if (m >= 7) {
+                uint32_t d[7];
+                float c[7][4];
+                sift_hip::ransac_draw7(seed, (uint32_t)s, it, (uint32_t)m, d);
+                for (int k = 0; k < 7; ++k)
+                    for (int e = 0; e < 4; ++e) c[k][e] = p[4 * (int64_t)d[k] + e];
+                mask = sift_hip::ransac_fundamental7(c, f);
+            }
+            for (int k = 0; k < 3; ++k) {
+                int32_t score = -1;
+                if ((mask >> k) & 1u) {
+                    score = 0;
+                    for (int64_t i = 0; i < m; ++i)
+                        score += sift_hip::ransac_fund_inlier(f[k], p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], thr2) ? 1 : 0;
+                }
+                if (scores) scores[((int64_t)s * iterations + it) * 3 + k] = score;
+                if (score > best_score) {   // strictly: the lowest slot keeps a tie
+                    best_score = score;
+                    for (int j = 0; j < 9; ++j) best.f[j] = f[k][j];
+                    best.inliers = score;
+                    best.iteration = (int32_t)it;
+                    best.root = k;
+                }
+            }
+        }
+        models[s] = best;
+        if (inlier)
+            for (int64_t i = 0; i < m; ++i)
+                inlier[offsets[s] + i] =
+                    best.iteration >= 0 && sift_hip::ransac_fund_inlier(best.f, p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], thr2) ? 1 : 0;
+    }
 }
 }

@@ -9,6 +9,7 @@
 // 64 rows) issues the same vector operations per predicate but pays a cross-lane step per hypothesis and wastes lanes on the
 // short lists (a few hundred rows) that a ratio test leaves; this one wastes lanes only below 256 iterations.
 #include "ransac_kernels.h"
+#include "ransac_fund_math.h"
 #include "ransac_math.h"
 #include "ransac_refine_math.h"
 
@@ -27,6 +28,31 @@ __device__ __forceinline__ int set_of_row(const int64_t* __restrict__ off, int n
     return lo;
 }
 }  // namespace
+
+// What the scoring, selection and flag kernels need to know of a model: its record, its predicate, and how many hypothesis
+// slots a sample yields.  The nine floats mean nothing to those kernels.
+struct HomographyModel {
+    typedef sift_hip_homography Rec;
+    static constexpr int kSlots = 1;
+    static __device__ __forceinline__ const float* coef(const Rec* r) { return r->h; }
+    static __device__ __forceinline__ float* coef(Rec* r) { return r->h; }
+    static __device__ __forceinline__ bool inlier(const float (&h)[9], float qx, float qy, float tx, float ty, float thr2) {
+        return ransac_inlier(h, qx, qy, tx, ty, thr2);
+    }
+    // the record's last field: refinement rounds
+    static __device__ __forceinline__ void finish(Rec* r, bool any, int win) { r->iteration = any ? win : -1; r->refined = 0; }
+};
+struct FundamentalModel {
+    typedef sift_hip_fundamental Rec;
+    static constexpr int kSlots = 3;
+    static __device__ __forceinline__ const float* coef(const Rec* r) { return r->f; }
+    static __device__ __forceinline__ float* coef(Rec* r) { return r->f; }
+    static __device__ __forceinline__ bool inlier(const float (&f)[9], float qx, float qy, float tx, float ty, float thr2) {
+        return ransac_fund_inlier(f, qx, qy, tx, ty, thr2);
+    }
+    // slot 3 * iteration + root
+    static __device__ __forceinline__ void finish(Rec* r, bool any, int win) { r->iteration = any ? win / 3 : -1; r->root = any ? win % 3 : -1; }
+};
 
 // one lane per (set, iteration): draw, gather four rows, solve in double
 __global__ __launch_bounds__(256) void ransac_hypothesis_kernel(const float* __restrict__ pts, const int64_t* __restrict__ off, int n_sets,
@@ -52,8 +78,46 @@ __global__ __launch_bounds__(256) void ransac_hypothesis_kernel(const float* __r
     hyp[gid] = out;
 }
 
+// One lane per (set, sample): draw, gather seven rows, solve in double, three records (slot 3 * sample + root).  The 7 x 9
+// doubles of the elimination live in registers (ransac_fund_math.h indexes them by select chains), which is what the launch
+// bound is sized for.
+__global__ __launch_bounds__(kFundLanes) void ransac_fund_hypothesis_kernel(const float* __restrict__ pts, const int64_t* __restrict__ off, int n_sets,
+                                                                            uint32_t iterations, uint32_t seed, RansacHyp* __restrict__ hyp) {
+    const long long gid = (long long)blockIdx.x * kFundLanes + threadIdx.x;
+    if (gid >= (long long)n_sets * iterations) return;
+    const int set = (int)(gid / iterations);
+    const uint32_t it = (uint32_t)(gid % iterations);
+    const int64_t row0 = off[set], m = off[set + 1] - row0;
+    float f[3][9];
+    uint32_t mask = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int j = 0; j < 9; ++j) f[k][j] = 0.0f;
+    if (m >= 7) {
+        uint32_t d[7];
+        float c[7][4];
+        ransac_draw7(seed, (uint32_t)set, it, (uint32_t)m, d);
+#pragma unroll
+        for (int k = 0; k < 7; ++k) {
+            const f4v r = *reinterpret_cast<const f4v*>(pts + 4 * (row0 + (int64_t)d[k]));
+            c[k][0] = r.x; c[k][1] = r.y; c[k][2] = r.z; c[k][3] = r.w;
+        }
+        mask = ransac_fundamental7(c, f);
+    }
+    RansacHyp* out = hyp + 3 * (size_t)gid;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+        for (int j = 0; j < 9; ++j) out[k].h[j] = f[k][j];
+        out[k].valid = (int32_t)((mask >> k) & 1u);
+    }
+}
+
+// `slots`: hypothesis slots per set (iterations x the model's slots per sample)
+template <typename Model>
 __global__ __launch_bounds__(kRansacHyps) void ransac_score_kernel(const float* __restrict__ pts, const RansacHyp* __restrict__ hyp,
-                                                                   const RansacTile* __restrict__ tiles, uint32_t iterations, float thr2,
+                                                                   const RansacTile* __restrict__ tiles, uint32_t slots, float thr2,
                                                                    int32_t* __restrict__ scores) {
     __shared__ __attribute__((aligned(16))) f4v rows[kRansacRows];
     const RansacTile t = tiles[blockIdx.x];
@@ -61,22 +125,23 @@ __global__ __launch_bounds__(kRansacHyps) void ransac_score_kernel(const float* 
     for (int i = threadIdx.x; i < n; i += kRansacHyps) rows[i] = *reinterpret_cast<const f4v*>(pts + 4 * ((size_t)t.row_lo + i));
     __syncthreads();
     const uint32_t it = (uint32_t)t.hyp0 + threadIdx.x;
-    if (it >= iterations) return;
-    const size_t slot = (size_t)t.set * iterations + it;
+    if (it >= slots) return;
+    const size_t slot = (size_t)t.set * slots + it;
     const RansacHyp me = hyp[slot];
     if (!me.valid) return;
     int count = 0;
 #pragma unroll 8
     for (int i = 0; i < n; ++i) {
         const f4v r = rows[i];
-        count += ransac_inlier(me.h, r.x, r.y, r.z, r.w, thr2) ? 1 : 0;
+        count += Model::inlier(me.h, r.x, r.y, r.z, r.w, thr2) ? 1 : 0;
     }
     if (count) atomicAdd(&scores[slot], count);   // the result is not used: an add without return
 }
 
-// one workgroup per set: -1 into the scores of invalid hypotheses, the argmax under (score descending, iteration ascending)
+// one workgroup per set: -1 into the scores of invalid hypotheses, the argmax under (score descending, slot ascending)
+template <typename Model>
 __global__ __launch_bounds__(256) void ransac_select_kernel(const RansacHyp* __restrict__ hyp, uint32_t iterations, int32_t* __restrict__ scores,
-                                                            sift_hip_homography* __restrict__ models) {
+                                                            typename Model::Rec* __restrict__ models) {
     __shared__ int s_score[256];
     __shared__ int s_iter[256];
     const int tid = threadIdx.x;
@@ -99,11 +164,10 @@ __global__ __launch_bounds__(256) void ransac_select_kernel(const RansacHyp* __r
     }
     const bool any = s_score[0] >= 0;
     const int win = s_iter[0];
-    sift_hip_homography* out = models + blockIdx.x;
-    if (tid < 9) out->h[tid] = any ? hyp[base + win].h[tid] : 0.0f;
+    typename Model::Rec* out = models + blockIdx.x;
+    if (tid < 9) Model::coef(out)[tid] = any ? hyp[base + win].h[tid] : 0.0f;
     if (tid == 9) out->inliers = any ? s_score[0] : 0;
-    if (tid == 10) out->iteration = any ? win : -1;
-    if (tid == 11) out->refined = 0;
+    if (tid == 10) Model::finish(out, any, win);
 }
 
 namespace {
@@ -256,18 +320,19 @@ __global__ __launch_bounds__(kRefineLanes) void ransac_refine_kernel(const float
 }
 
 // one lane per row: the predicate under the winner of the row's set
+template <typename Model>
 __global__ __launch_bounds__(256) void ransac_flags_kernel(const float* __restrict__ pts, const int64_t* __restrict__ off, int n_sets, long long rows,
-                                                           const sift_hip_homography* __restrict__ models, float thr2, uint8_t* __restrict__ inlier) {
+                                                           const typename Model::Rec* __restrict__ models, float thr2, uint8_t* __restrict__ inlier) {
     const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
     if (row >= rows) return;
     bool in = false;
     if (row >= off[0]) {
-        const sift_hip_homography* mdl = models + set_of_row(off, n_sets, row);
+        const typename Model::Rec* mdl = models + set_of_row(off, n_sets, row);
         if (mdl->iteration >= 0) {
             float h[9];
-            for (int k = 0; k < 9; ++k) h[k] = mdl->h[k];
+            for (int k = 0; k < 9; ++k) h[k] = Model::coef(mdl)[k];
             const f4v r = *reinterpret_cast<const f4v*>(pts + 4 * (size_t)row);
-            in = ransac_inlier(h, r.x, r.y, r.z, r.w, thr2);
+            in = Model::inlier(h, r.x, r.y, r.z, r.w, thr2);
         }
     }
     inlier[row] = in ? 1 : 0;
@@ -299,11 +364,11 @@ void launch_ransac_hypotheses(hipStream_t s, const float* d_pts, const int64_t* 
 void launch_ransac_score(hipStream_t s, const float* d_pts, const RansacHyp* d_hyp, const RansacTile* d_tiles, int n_tiles, uint32_t iterations,
                          float thr2, int32_t* d_scores) {
     if (n_tiles <= 0) return;
-    hipLaunchKernelGGL(ransac_score_kernel, dim3((unsigned)n_tiles), dim3(kRansacHyps), 0, s, d_pts, d_hyp, d_tiles, iterations, thr2, d_scores);
+    hipLaunchKernelGGL(ransac_score_kernel<HomographyModel>, dim3((unsigned)n_tiles), dim3(kRansacHyps), 0, s, d_pts, d_hyp, d_tiles, iterations, thr2, d_scores);
 }
 void launch_ransac_select(hipStream_t s, const RansacHyp* d_hyp, int n_sets, uint32_t iterations, int32_t* d_scores, sift_hip_homography* d_models) {
     if (n_sets <= 0) return;
-    hipLaunchKernelGGL(ransac_select_kernel, dim3((unsigned)n_sets), dim3(256), 0, s, d_hyp, iterations, d_scores, d_models);
+    hipLaunchKernelGGL(ransac_select_kernel<HomographyModel>, dim3((unsigned)n_sets), dim3(256), 0, s, d_hyp, iterations, d_scores, d_models);
 }
 void launch_ransac_refine(hipStream_t s, const float* d_pts, const int64_t* d_off, int n_sets, int rounds, float thr2, sift_hip_homography* d_models) {
     if (n_sets <= 0) return;
@@ -312,7 +377,28 @@ void launch_ransac_refine(hipStream_t s, const float* d_pts, const int64_t* d_of
 void launch_ransac_flags(hipStream_t s, const float* d_pts, const int64_t* d_off, int n_sets, long long rows, const sift_hip_homography* d_models,
                          float thr2, uint8_t* d_inlier) {
     if (rows <= 0 || n_sets <= 0) return;
-    hipLaunchKernelGGL(ransac_flags_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, d_pts, d_off, n_sets, rows, d_models, thr2, d_inlier);
+    hipLaunchKernelGGL(ransac_flags_kernel<HomographyModel>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, d_pts, d_off, n_sets, rows, d_models, thr2, d_inlier);
+}
+void launch_fund_hypotheses(hipStream_t s, const float* d_pts, const int64_t* d_off, int n_sets, uint32_t iterations, uint32_t seed, RansacHyp* d_hyp) {
+    const long long n = (long long)n_sets * iterations;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(ransac_fund_hypothesis_kernel, dim3((unsigned)((n + kFundLanes - 1) / kFundLanes)), dim3(kFundLanes), 0, s, d_pts, d_off, n_sets,
+                       iterations, seed, d_hyp);
+}
+void launch_fund_score(hipStream_t s, const float* d_pts, const RansacHyp* d_hyp, const RansacTile* d_tiles, int n_tiles, uint32_t slots, float thr2,
+                       int32_t* d_scores) {
+    if (n_tiles <= 0) return;
+    hipLaunchKernelGGL(ransac_score_kernel<FundamentalModel>, dim3((unsigned)n_tiles), dim3(kRansacHyps), 0, s, d_pts, d_hyp, d_tiles, slots, thr2, d_scores);
+}
+void launch_fund_select(hipStream_t s, const RansacHyp* d_hyp, int n_sets, uint32_t slots, int32_t* d_scores, sift_hip_fundamental* d_models) {
+    if (n_sets <= 0) return;
+    hipLaunchKernelGGL(ransac_select_kernel<FundamentalModel>, dim3((unsigned)n_sets), dim3(256), 0, s, d_hyp, slots, d_scores, d_models);
+}
+void launch_fund_flags(hipStream_t s, const float* d_pts, const int64_t* d_off, int n_sets, long long rows, const sift_hip_fundamental* d_models,
+                       float thr2, uint8_t* d_inlier) {
+    if (rows <= 0 || n_sets <= 0) return;
+    hipLaunchKernelGGL(ransac_flags_kernel<FundamentalModel>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, d_pts, d_off, n_sets, rows, d_models, thr2,
+                       d_inlier);
 }
 void launch_ransac_gather(hipStream_t s, const sift_hip_match_rec* d_recs, const int64_t* d_off, int n_pairs, long long rows,
                           const sift_hip_keypoint* d_kp, const int* d_kp_row0, float coord_scale, float* d_pts) {

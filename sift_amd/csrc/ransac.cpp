@@ -1,4 +1,5 @@
-// Host side of the geometric verification (include/sift_hip.h: sift_hip_ransac_homography, sift_hip_result_verify): staging of
+// Host side of the geometric verification (include/sift_hip.h: sift_hip_ransac_homography, sift_hip_result_verify, and their
+// fundamental-matrix counterparts sift_hip_ransac_fundamental, sift_hip_result_verify_fundamental): staging of
 // caller memory, the tile table that makes all sets one launch of the scoring kernel, and the scratch memory, which the first call
 // of a context allocates and the context keeps - outside the batch arena, like the matcher's.
 #include <algorithm>
@@ -62,7 +63,7 @@ struct Job {
     int n_sets;
     const int64_t* offsets;
     const sift_hip_ransac_params* params;
-    sift_hip_homography* models;
+    void* models;               // sift_hip_homography, or sift_hip_fundamental when `fund`: records of one size
     uint8_t* inlier;
     int32_t* scores;
     char* err;
@@ -70,6 +71,7 @@ struct Job {
     bool refine_only = false;   // sift_hip_refine_homography: `models` are the caller's, no sampling; params is null
     float threshold = 0.0f;     //   its threshold and rounds
     int rounds = 0;
+    bool fund = false;          // the fundamental matrix: seven-point samples, three hypothesis slots per sample, no refinement
 };
 
 int run(void* arg) {
@@ -83,6 +85,8 @@ int run(void* arg) {
         if (j.rounds < 0 || j.rounds > 8) return fail(j.err, j.errlen, "sift_hip ransac: rounds must be 0 .. 8");
     } else if (const int rc = check_params(j.params, j.err, j.errlen)) {
         return rc;
+    } else if (j.fund && j.params->refine != 0) {
+        return fail(j.err, j.errlen, "sift_hip ransac: refine must be 0 for the fundamental matrix (no least-squares refit of F)");
     }
     if (j.n_sets < 0 || (j.n_sets > 0 && (!j.offsets || !j.models))) return fail(j.err, j.errlen, "sift_hip ransac: bad set arguments");
     if (j.n_sets == 0) return SIFT_HIP_OK;
@@ -93,7 +97,9 @@ int run(void* arg) {
     if (rows > 0x7fffffffLL / 4) return fail(j.err, j.errlen, "sift_hip ransac: too many rows");
     if (rows > 0 && !j.pts && !j.gather) return fail(j.err, j.errlen, "sift_hip ransac: no rows");
     const uint32_t iters = j.refine_only ? 0u : j.params->iterations;
-    const long long n_hyp = (long long)j.n_sets * iters;
+    const uint32_t slots = iters * (j.fund ? 3u : 1u);   // hypotheses per set
+    const long long min_rows = j.fund ? kFundMinRows : kHomographyMinRows;
+    const long long n_hyp = (long long)j.n_sets * slots;
     if (n_hyp > 0x7fffffffLL / 2) return fail(j.err, j.errlen, "sift_hip ransac: too many hypotheses (sets x iterations)");
     const float thr = j.refine_only ? j.threshold : j.params->threshold, thr2 = thr * thr;
     const int rounds = j.refine_only ? j.rounds : (int)j.params->refine;
@@ -103,15 +109,15 @@ int run(void* arg) {
     long long n_tiles = 0;
     for (int s = 0; s < j.n_sets; ++s) {
         const long long m = j.offsets[s + 1] - j.offsets[s];
-        if (m >= 4 && !j.refine_only) n_tiles += ((iters + kRansacHyps - 1) / kRansacHyps) * ((m + kRansacRows - 1) / kRansacRows);
+        if (m >= min_rows && !j.refine_only) n_tiles += ((slots + kRansacHyps - 1) / kRansacHyps) * ((m + kRansacRows - 1) / kRansacRows);
     }
     if (n_tiles > 0x7fffffffLL / 16) return fail(j.err, j.errlen, "sift_hip ransac: too many tiles");
     tiles.reserve((size_t)n_tiles);
     for (int s = 0; s < j.n_sets; ++s) {
         const long long r0 = j.offsets[s], m = j.offsets[s + 1] - r0;
-        if (m < 4 || j.refine_only) continue;   // no hypothesis of such a set is valid
+        if (m < min_rows || j.refine_only) continue;   // no hypothesis of such a set is valid
         for (long long lo = 0; lo < m; lo += kRansacRows)
-            for (uint32_t h0 = 0; h0 < iters; h0 += kRansacHyps)
+            for (uint32_t h0 = 0; h0 < slots; h0 += kRansacHyps)
                 tiles.push_back(RansacTile{s, (int)h0, (int)(r0 + lo), (int)(r0 + std::min<long long>(m, lo + kRansacRows))});
     }
 
@@ -164,7 +170,9 @@ int run(void* arg) {
     if (!models_direct) st.d_models.ensure((size_t)j.n_sets * sizeof(sift_hip_homography));
     if (j.inlier && !inlier_direct) st.d_inlier.ensure((size_t)std::max<long long>(rows, 1));
     int32_t* d_scores = scores_direct ? j.scores : st.d_scores.as<int32_t>();
-    sift_hip_homography* d_models = models_direct ? j.models : st.d_models.as<sift_hip_homography>();
+    void* d_models = models_direct ? j.models : st.d_models.p;
+    sift_hip_homography* d_hmodels = static_cast<sift_hip_homography*>(d_models);
+    sift_hip_fundamental* d_fmodels = static_cast<sift_hip_fundamental*>(d_models);
     uint8_t* d_inlier = inlier_direct ? j.inlier : st.d_inlier.as<uint8_t>();
 
     // ---- the launches: one of each kernel, whatever the number of sets ----
@@ -176,15 +184,21 @@ int run(void* arg) {
             match_upload(j.c, d_models, j.models, (size_t)j.n_sets * sizeof(sift_hip_homography));
             match_wait(j.c);
         }
+    } else if (j.fund) {
+        SIFT_HIP_CHECK(hipMemsetAsync(d_scores, 0, (size_t)n_hyp * sizeof(int32_t), v.stream));
+        launch_fund_hypotheses(v.stream, d_pts, st.d_off.as<int64_t>(), j.n_sets, iters, j.params->seed, st.d_hyp.as<RansacHyp>());
+        launch_fund_score(v.stream, d_pts, st.d_hyp.as<RansacHyp>(), st.d_tiles.as<RansacTile>(), (int)tiles.size(), slots, thr2, d_scores);
+        launch_fund_select(v.stream, st.d_hyp.as<RansacHyp>(), j.n_sets, slots, d_scores, d_fmodels);
     } else {
         SIFT_HIP_CHECK(hipMemsetAsync(d_scores, 0, (size_t)n_hyp * sizeof(int32_t), v.stream));
         launch_ransac_hypotheses(v.stream, d_pts, st.d_off.as<int64_t>(), j.n_sets, iters, j.params->seed, st.d_hyp.as<RansacHyp>());
         launch_ransac_score(v.stream, d_pts, st.d_hyp.as<RansacHyp>(), st.d_tiles.as<RansacTile>(), (int)tiles.size(), iters, thr2, d_scores);
-        launch_ransac_select(v.stream, st.d_hyp.as<RansacHyp>(), j.n_sets, iters, d_scores, d_models);
+        launch_ransac_select(v.stream, st.d_hyp.as<RansacHyp>(), j.n_sets, iters, d_scores, d_hmodels);
     }
     // every round of every set in one launch; with refine 0 the models are the selection's
-    if (j.refine_only || rounds > 0) launch_ransac_refine(v.stream, d_pts, st.d_off.as<int64_t>(), j.n_sets, rounds, thr2, d_models);
-    if (j.inlier) launch_ransac_flags(v.stream, d_pts, st.d_off.as<int64_t>(), j.n_sets, rows, d_models, thr2, d_inlier);
+    if (j.refine_only || rounds > 0) launch_ransac_refine(v.stream, d_pts, st.d_off.as<int64_t>(), j.n_sets, rounds, thr2, d_hmodels);
+    if (j.inlier && j.fund) launch_fund_flags(v.stream, d_pts, st.d_off.as<int64_t>(), j.n_sets, rows, d_fmodels, thr2, d_inlier);
+    if (j.inlier && !j.fund) launch_ransac_flags(v.stream, d_pts, st.d_off.as<int64_t>(), j.n_sets, rows, d_hmodels, thr2, d_inlier);
     SIFT_HIP_CHECK(hipGetLastError());
 
     if (!models_direct) match_download(j.c, j.models, d_models, (size_t)j.n_sets * sizeof(sift_hip_homography));
@@ -218,16 +232,25 @@ int sift_hip_refine_homography(sift_hip_ctx* c, const float* pts, int n_sets, co
     return match_guarded(err, errlen, run, &j);
 }
 
-int sift_hip_result_verify(sift_hip_ctx* c, int n_pairs, const int32_t* pair_q, const int32_t* pair_t, const sift_hip_match_params* match_params,
-                           const sift_hip_ransac_params* ransac_params, sift_hip_match_rec* recs, int32_t* counts, int64_t* total,
-                           sift_hip_homography* models, uint8_t* inlier, char* err, int errlen) {
-    if (!c) { match_set_err(err, errlen, "sift_hip_result_verify: no context (the verification runs on the GPU only)"); return SIFT_HIP_EINVAL; }
-    if (!match_params) { match_set_err(err, errlen, "sift_hip_result_verify: no match parameters"); return SIFT_HIP_EINVAL; }
+}  // extern "C"
+
+// sift_hip_result_verify and sift_hip_result_verify_fundamental: the match, then the model over the gathered coordinates
+static int result_verify(bool fund, sift_hip_ctx* c, int n_pairs, const int32_t* pair_q, const int32_t* pair_t, const sift_hip_match_params* match_params,
+                         const sift_hip_ransac_params* ransac_params, sift_hip_match_rec* recs, int32_t* counts, int64_t* total, void* models,
+                         uint8_t* inlier, char* err, int errlen) {
+    const char* who = fund ? "sift_hip_result_verify_fundamental" : "sift_hip_result_verify";
+    const auto bad = [&](const char* what) {
+        match_set_err(err, errlen, (std::string(who) + ": " + what).c_str());
+        return SIFT_HIP_EINVAL;
+    };
+    if (!c) return bad("no context (the verification runs on the GPU only)");
+    if (!match_params) return bad("no match parameters");
     if (const int rc = check_params(ransac_params, err, errlen)) return rc;
-    if (n_pairs > 0 && !models) { match_set_err(err, errlen, "sift_hip_result_verify: no model array"); return SIFT_HIP_EINVAL; }
+    if (fund && ransac_params->refine != 0) return fail(err, errlen, "sift_hip ransac: refine must be 0 for the fundamental matrix (no least-squares refit of F)");
+    if (n_pairs > 0 && !models) return bad("no model array");
     std::vector<int32_t> host_counts((size_t)std::max(n_pairs, 0), 0);
     const sift_hip_match_rec* d_recs = nullptr;
-    const int rc = match_result_on_device(c, "sift_hip_result_verify", n_pairs, pair_q, pair_t, match_params, recs, counts, total, &d_recs,
+    const int rc = match_result_on_device(c, who, n_pairs, pair_q, pair_t, match_params, recs, counts, total, &d_recs,
                                           host_counts.data(), err, errlen);
     if (rc != SIFT_HIP_OK || n_pairs <= 0) return rc;
     // pair p is set p: its rows are its records; the keypoints of a record are rows of the pair's two images
@@ -243,7 +266,30 @@ int sift_hip_result_verify(sift_hip_ctx* c, int n_pairs, const int32_t* pair_q, 
     }
     const Gather g{d_recs, v.d_kp, kp_row0.data(), ransac_ctx_subpixel(c) ? 0.5f : 1.0f};
     Job j{c, nullptr, &g, n_pairs, offsets.data(), ransac_params, models, inlier, nullptr, err, errlen};
+    j.fund = fund;
     return match_guarded(err, errlen, run, &j);
+}
+
+extern "C" {
+
+int sift_hip_result_verify(sift_hip_ctx* c, int n_pairs, const int32_t* pair_q, const int32_t* pair_t, const sift_hip_match_params* match_params,
+                           const sift_hip_ransac_params* ransac_params, sift_hip_match_rec* recs, int32_t* counts, int64_t* total,
+                           sift_hip_homography* models, uint8_t* inlier, char* err, int errlen) {
+    return result_verify(false, c, n_pairs, pair_q, pair_t, match_params, ransac_params, recs, counts, total, models, inlier, err, errlen);
+}
+
+int sift_hip_ransac_fundamental(sift_hip_ctx* c, const float* pts, int n_sets, const int64_t* offsets, const sift_hip_ransac_params* params,
+                                sift_hip_fundamental* models, uint8_t* inlier, int32_t* scores, char* err, int errlen) {
+    if (!c) { match_set_err(err, errlen, "sift_hip_ransac_fundamental: no context (the verification runs on the GPU only)"); return SIFT_HIP_EINVAL; }
+    Job j{c, pts, nullptr, n_sets, offsets, params, models, inlier, scores, err, errlen};
+    j.fund = true;
+    return match_guarded(err, errlen, run, &j);
+}
+
+int sift_hip_result_verify_fundamental(sift_hip_ctx* c, int n_pairs, const int32_t* pair_q, const int32_t* pair_t, const sift_hip_match_params* match_params,
+                                       const sift_hip_ransac_params* ransac_params, sift_hip_match_rec* recs, int32_t* counts, int64_t* total,
+                                       sift_hip_fundamental* models, uint8_t* inlier, char* err, int errlen) {
+    return result_verify(true, c, n_pairs, pair_q, pair_t, match_params, ransac_params, recs, counts, total, models, inlier, err, errlen);
 }
 
 }  // extern "C"

@@ -30,6 +30,19 @@ void launch_ransac_select(hipStream_t s, const RansacHyp* d_hyp, int n_sets, uin
 void launch_ransac_refine(hipStream_t s, const float* d_pts, const int64_t* d_off, int n_sets, int rounds, float thr2, sift_hip_homography* d_models);
 void launch_ransac_flags(hipStream_t s, const float* d_pts, const int64_t* d_off, int n_sets, long long rows, const sift_hip_homography* d_models,
                          float thr2, uint8_t* d_inlier);
+// ---- the fundamental matrix (ransac_fund_math.h): the same scoring, selection and flag kernels, instantiated with its
+// predicate, over 3 * iterations hypothesis slots per set (slot 3 * sample + root); RansacHyp's h holds f ----
+constexpr int kFundLanes = 256;      // lanes of a workgroup of the seven-point solver: one per (set, sample)
+constexpr int kFundMinRows = 7, kHomographyMinRows = 4;
+static_assert(sizeof(sift_hip_fundamental) == 48, "ransac record packing");
+// d_hyp: n_sets x 3 * iterations records
+void launch_fund_hypotheses(hipStream_t s, const float* d_pts, const int64_t* d_off, int n_sets, uint32_t iterations, uint32_t seed, RansacHyp* d_hyp);
+// the tiles' hyp0 counts slots; d_scores (n_sets x slots) must be zero
+void launch_fund_score(hipStream_t s, const float* d_pts, const RansacHyp* d_hyp, const RansacTile* d_tiles, int n_tiles, uint32_t slots, float thr2,
+                       int32_t* d_scores);
+void launch_fund_select(hipStream_t s, const RansacHyp* d_hyp, int n_sets, uint32_t slots, int32_t* d_scores, sift_hip_fundamental* d_models);
+void launch_fund_flags(hipStream_t s, const float* d_pts, const int64_t* d_off, int n_sets, long long rows, const sift_hip_fundamental* d_models,
+                       float thr2, uint8_t* d_inlier);
 // rows of sift_hip_result_verify: record i of pair p (d_off: the pairs' record offsets) -> (qx, qy, tx, ty); d_kp_row0: for
 // every pair the first keypoint row of its query image and of its train image (2 ints per pair)
 void launch_ransac_gather(hipStream_t s, const sift_hip_match_rec* d_recs, const int64_t* d_off, int n_pairs, long long rows,

@@ -13,7 +13,8 @@
 //              when no hypothesis is valid or the set has fewer than four rows.  The flags are the predicate under the winner.
 // Scores are integers: the result cannot depend on how rows or hypotheses are tiled, split over workgroups or reduced.
 // The H these functions select is the best MINIMAL-SAMPLE model; its least-squares refit over the inliers, with sums in a fixed
-// order so that it stays bit-defined, is ransac_refine_math.h.  There is no adaptive early stop and no other model.
+// order so that it stays bit-defined, is ransac_refine_math.h.  There is no adaptive early stop.  The other model, the
+// fundamental matrix from seven-point samples, is ransac_fund_math.h; it shares the hash and the selection rule.
 #pragma once
 #include <stdint.h>
 

@@ -474,6 +474,32 @@ class Context:
             _raise(rc, err)
         return (models, inlier, scores) if scores is not None else (models, inlier)
 
+    def ransac_fundamental(self, pts, offsets=None, iterations=2048, threshold=3.0, seed=0, want_scores=False, models_out=None,
+                           inlier_out=None, scores_out=None, refine=0):
+        """sift_hip_ransac_fundamental: the best seven-point fundamental matrix of every set of correspondences (qx, qy, tx, ty),
+        (tx, ty, 1) F (qx, qy, 1)^T = 0 -> (models, inlier[, scores]): models[s] = (f [9] row-major, inliers, iteration; -1: none,
+        root), inlier one byte per row, scores [n_sets, 3 * iterations] with `want_scores` (slot 3 * sample + root).  Arguments as
+        for ransac_homography; `refine` must be 0 (there is no least-squares refit of F)."""
+        if isinstance(pts, np.ndarray):
+            pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 4)
+        if offsets is None:
+            offsets = [0, pts.shape[0]]
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        n_sets = max(offsets.size - 1, 0)
+        rows = int(offsets[-1]) if offsets.size and offsets[-1] > 0 else 0
+        models = np.zeros(n_sets, _lib.FUNDAMENTAL_DTYPE) if models_out is None else models_out
+        inlier = np.zeros(rows, np.uint8) if inlier_out is None else inlier_out
+        scores = scores_out
+        if scores is None and want_scores:
+            scores = np.zeros((n_sets, 3 * int(iterations) if 0 < iterations <= 65536 else 0), np.int32)   # out of range: the call says so
+        prm = _lib.RansacParams(int(iterations) & 0xffffffff, int(seed) & 0xffffffff, float(threshold), int(refine) & 0xffffffff)
+        err = C.create_string_buffer(512)
+        rc = self._L.sift_hip_ransac_fundamental(self._h, self._addr(pts), n_sets, offsets, C.byref(prm), self._addr(models), self._addr(inlier),
+                                                 self._addr(scores), err, 512)
+        if rc:
+            _raise(rc, err)
+        return (models, inlier, scores) if scores is not None else (models, inlier)
+
     def refine_homography(self, pts, models, offsets=None, threshold=3.0, rounds=2, inlier_out=None):
         """sift_hip_refine_homography: at most `rounds` (0 .. 8) rounds of least-squares re-estimation of given models over their
         own inliers, no sampling -> (models, inlier).  `models`: a HOMOGRAPHY_DTYPE array (copied; h and iteration are read, a
@@ -497,23 +523,28 @@ class Context:
             _raise(rc, err)
         return models, inlier
 
-    def verify_images(self, pairs, ratio=0.8, cross_check=False, iterations=2048, threshold=3.0, seed=0, refine=0):
+    def verify_images(self, pairs, ratio=0.8, cross_check=False, iterations=2048, threshold=3.0, seed=0, refine=0, model="homography"):
         """sift_hip_result_verify: match_images followed by ransac_homography on the matches' image coordinates, all on the
         device-resident results -> (records, counts, models, inlier): models[p] belongs to pair p, inlier[i] to records[i].
-        `refine` as for ransac_homography."""
+        `refine` as for ransac_homography.  model="fundamental": sift_hip_result_verify_fundamental, ransac_fundamental in
+        place of ransac_homography (models of FUNDAMENTAL_DTYPE; `refine` must be 0)."""
+        if model not in ("homography", "fundamental"):
+            raise ValueError('verify_images: model must be "homography" or "fundamental"')
+        fund = model == "fundamental"
         pq, pt = self._pairs(pairs)
         cnt = self.counts() if self._L.sift_hip_result_images(self._h) >= 0 else np.zeros(0, np.int32)   # none: the call says so
         rows = int(sum(cnt[q] for q in pq if 0 <= q < cnt.size))
         recs = np.zeros(rows, _lib.MATCH_DTYPE)
         inlier = np.zeros(rows, np.uint8)
-        models = np.zeros(pq.size, _lib.HOMOGRAPHY_DTYPE)
+        models = np.zeros(pq.size, _lib.FUNDAMENTAL_DTYPE if fund else _lib.HOMOGRAPHY_DTYPE)
         counts = np.zeros(pq.size, np.int32)
         total = C.c_int64()
         mprm = _lib.MatchParams(float(ratio), 1 if cross_check else 0)
         rprm = _lib.RansacParams(int(iterations) & 0xffffffff, int(seed) & 0xffffffff, float(threshold), int(refine) & 0xffffffff)
         err = C.create_string_buffer(512)
-        rc = self._L.sift_hip_result_verify(self._h, pq.size, pq, pt, C.byref(mprm), C.byref(rprm), C.c_void_p(recs.ctypes.data), counts,
-                                            C.byref(total), C.c_void_p(models.ctypes.data), C.c_void_p(inlier.ctypes.data), err, 512)
+        call = self._L.sift_hip_result_verify_fundamental if fund else self._L.sift_hip_result_verify
+        rc = call(self._h, pq.size, pq, pt, C.byref(mprm), C.byref(rprm), C.c_void_p(recs.ctypes.data), counts, C.byref(total),
+                  C.c_void_p(models.ctypes.data), C.c_void_p(inlier.ctypes.data), err, 512)
         if rc:
             _raise(rc, err)
         return recs[:total.value], counts, models, inlier[:total.value]
@@ -703,11 +734,15 @@ class Sift:
         return self.ctx.match(qa, qb, ratio, cross_check, ka, kb)
 
     def verify(self, points_a, points_b, ratio: float = 0.8, cross_check: bool = False, iterations: int = 2048, threshold: float = 3.0,
-               seed: int = 0, refine: int = 0):
+               seed: int = 0, refine: int = 0, model: str = "homography"):
         """match() followed by the geometric check of its list (an extension) -> (records, model, inlier): the best four-point
         homography from image a to image b over the matches' image coordinates (loc * 2^octave, halved with subpixel), as one
         record (h [9] row-major, inliers, iteration; -1: none, refined), and one flag per record.  `refine`: rounds of
-        least-squares re-estimation over the inliers, 0 .. 8 (0: the minimal-sample model)."""
+        least-squares re-estimation over the inliers, 0 .. 8 (0: the minimal-sample model).  model="fundamental": the best
+        seven-point fundamental matrix instead, (tb, 1) F (ta, 1)^T = 0, as one record (f [9], inliers, iteration, root); the
+        right model for two views of a general scene, where a homography explains one plane only.  `refine` must then be 0."""
+        if model not in ("homography", "fundamental"):
+            raise ValueError('verify: model must be "homography" or "fundamental"')
         recs = self.match(points_a, points_b, ratio, cross_check)
         scale = np.float32(0.5 if self.subpixel else 1.0)
 
@@ -715,5 +750,6 @@ class Sift:
             xy = np.array([[points[i].loc[0] << points[i].octave, points[i].loc[1] << points[i].octave] for i in which], np.float32)
             return xy.reshape(-1, 2) * scale
         pts = np.concatenate([coords(points_a, recs["query"]), coords(points_b, recs["train"])], axis=1)
-        models, inlier = self.ctx.ransac_homography(pts, None, iterations, threshold, seed, refine=refine)
+        run = self.ctx.ransac_fundamental if model == "fundamental" else self.ctx.ransac_homography
+        models, inlier = run(pts, None, iterations, threshold, seed, refine=refine)
         return recs, models[0], inlier

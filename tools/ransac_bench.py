@@ -19,8 +19,15 @@ refined models and flags bit for bit with the host loop (hostmath_ransac_homogra
 the minimal-sample and the refined model on the synthetic case of tests/test_refine_host.py (600 rows, 60 % outliers, 0.5 px
 noise, 512 hypotheses, seeds 0 .. 19, `refine` 8).  It APPENDS its lines to --out.
 
+The fundamental arm (--fundamental-arm) runs the same three RANSAC-alone cases through sift_hip_ransac_fundamental (seven-point
+samples, 3 x iterations hypothesis slots per set), alternating with sift_hip_ransac_homography at the same iterations on the same
+GPU, beside the host loop (hostmath_ransac_fundamental) on one core; models and flags are compared bit for bit with that loop.
+The rows are those of the homography cases: the question is what the call costs, not whether the scenes determine F.  It
+APPENDS its lines to --out.
+
     python tools/ransac_bench.py [--reps 20] [--frames 32] [--out profiles/ransac_bench.txt]
     python tools/ransac_bench.py --refine-arm [--reps 20] [--out profiles/ransac_bench.txt]
+    python tools/ransac_bench.py --fundamental-arm [--reps 20] [--out profiles/ransac_bench.txt]
 """
 import argparse
 import json
@@ -48,11 +55,14 @@ def main():
     ap.add_argument("--iterations", type=int, default=2048)
     ap.add_argument("--out", default=None)
     ap.add_argument("--refine-arm", action="store_true", help="only the refine arm: refine 0 against refine 2, appended to --out")
+    ap.add_argument("--fundamental-arm", action="store_true",
+                    help="only the fundamental arm: sift_hip_ransac_fundamental against sift_hip_ransac_homography, appended to --out")
     args = ap.parse_args()
 
     import torch
     import ransac_ref as R
     import refine_ref as F
+    import fund_ref
     from sift_amd import _lib
     from sift_amd.sift import Context, K_SQRT2
     from sift_amd.synthetic import synth_batch
@@ -144,6 +154,26 @@ def main():
               "added_ms_median": round(fine["median_ms"] - plain["median_ms"], 4), "rounds_accepted": want[0]["refined"].tolist()[:8],
               "inliers_minimal": base[0]["inliers"].tolist()[:8], "inliers_refined": want[0]["inliers"].tolist()[:8]})
 
+    def fund_case(name, ctx, pts, off):
+        """sift_hip_ransac_fundamental and sift_hip_ransac_homography at the same iterations, alternating; rows and results on the device."""
+        n_sets = off.size - 1
+        dpts = torch.from_numpy(pts).cuda()
+        dm = torch.zeros((n_sets, 12), dtype=torch.int32, device="cuda")
+        dh = torch.zeros((n_sets, 12), dtype=torch.int32, device="cuda")
+        df = torch.zeros((max(pts.shape[0], 1),), dtype=torch.uint8, device="cuda")
+        dg = torch.zeros((max(pts.shape[0], 1),), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        fund, homo = race(lambda: ctx.ransac_fundamental(dpts, off, its, thr, 0, models_out=dm, inlier_out=df),
+                          lambda: ctx.ransac_homography(dpts, off, its, thr, 0, models_out=dh, inlier_out=dg))
+        host = timed(lambda: fund_ref.ransac(pts, off, its, thr, 0), 3)
+        want = fund_ref.ransac(pts, off, its, thr, 0)
+        ok = dm.cpu().numpy().tobytes() == want[0].tobytes() and df.cpu().numpy()[:pts.shape[0]].tobytes() == want[1].tobytes()
+        emit({"case": "fundamental arm, " + name, "sets": int(n_sets), "rows": int(pts.shape[0]), "iterations": its, "slots_per_set": 3 * its,
+              "valid_share": round(float((want[2] >= 0).mean()), 3), "inliers": want[0]["inliers"].tolist()[:4],
+              "bitwise_equal_to_host_loop": bool(ok), "fundamental": fund, "homography_same_iterations": homo, "host_loop_one_core": host,
+              "ratio_to_homography": round(fund["median_ms"] / homo["median_ms"], 2),
+              "speedup_vs_host_loop": round(host["median_ms"] / fund["median_ms"], 1)})
+
     def finish(mode, header):
         if args.out:
             with open(args.out, mode) as f:
@@ -161,6 +191,21 @@ def main():
     # ---- (a): two 1080p frames' match list ----
     rec, counts = ctx.match_images([(0, 1)], 0.8, False)
     pts = np.concatenate([coords(kp, row0[0], rec["query"]), coords(kp, row0[1], rec["train"])], axis=1)
+    if args.fundamental_arm:
+        fund_case("a: match list of frames 1 and 2 of the bench batch", ctx, pts, np.array([0, pts.shape[0]], np.int64))
+        pairs = [(i, i + 1) for i in range(n - 1)]
+        rec, counts = ctx.match_images(pairs, 0.8, False)
+        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        pts = np.zeros((rec.size, 4), np.float32)
+        for p, (a, b) in enumerate(pairs):
+            r = rec[off[p]:off[p + 1]]
+            pts[off[p]:off[p + 1]] = np.concatenate([coords(kp, row0[a], r["query"]), coords(kp, row0[b], r["train"])], axis=1)
+        fund_case(f"b: the {len(pairs)} lists of consecutive pairs as the sets of one call", ctx, pts, off)
+        rows, _ = R.projective_rows(np.random.default_rng(0), 20000)
+        fund_case("c: 20 000 synthetic correspondences (60 % outliers)", ctx, rows, np.array([0, 20000], np.int64))
+        ctx.close()
+        finish("a", [])
+        return
     if args.refine_arm:
         refine_case("a: match list of frames 1 and 2 of the bench batch", ctx, pts, np.array([0, pts.shape[0]], np.int64))
         pairs = [(i, i + 1) for i in range(n - 1)]
