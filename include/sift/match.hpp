@@ -53,14 +53,7 @@ public:
     std::vector<Match> match(const std::vector<InterestPoint>& query, const std::vector<InterestPoint>& train, f32_t ratio = 0.8f,
                              bool crossCheck = false) {
         const size_t nq = query.size(), nt = train.size();
-        _desc.assign((nq + nt) * 128, 0.0f);
-        _kp.assign(nq + nt, sift_hip_keypoint{});
-        for (size_t i = 0; i < nq + nt; ++i) {
-            const InterestPoint& p = i < nq ? query[i] : train[i - nq];
-            if (p.descriptors.size() != 128) continue;
-            _kp[i].has_descriptor = 1;
-            for (size_t k = 0; k < 128; ++k) _desc[i * 128 + k] = p.descriptors[k];
-        }
+        rows(query, train);
         const int64_t offsets[3] = {0, (int64_t)nq, (int64_t)(nq + nt)};
         const int32_t pq = 0, pt = 1;
         sift_hip_match_params prm{};
@@ -73,14 +66,23 @@ public:
         const int rc = sift_hip_match(_ctx, _desc.data(), _kp.data(), 2, offsets, 1, &pq, &pt, &prm, _recs.data(), &count, &total, err, sizeof(err));
         if (rc == SIFT_HIP_EINVAL) throw std::invalid_argument(err);
         if (rc != SIFT_HIP_OK) throw std::runtime_error(err);
-        std::vector<Match> out((size_t)total);
-        for (size_t i = 0; i < out.size(); ++i) {
-            out[i].query = _recs[i].query;
-            out[i].train = _recs[i].train;
-            out[i].dist2 = _recs[i].dist2;
-            out[i].second2 = _recs[i].second2;
-        }
-        return out;
+        return records((size_t)total);
+    }
+
+    // Guided matching (include/sift_hip.h, "guided matching"): match() again under a verified model.  A train point competes for
+    // a query point only when it lies within `threshold` pixels of the model - of the transferred point for a Homography, of the
+    // epipolar line (Sampson distance) for a Fundamental - so "best" and "second best" are taken among those points alone, and so
+    // is the best query point seen from a train point (crossCheck).  Repeated structure, which the plain ratio test drops, comes
+    // back.  Coordinates as verify() forms them: loc * 2^octave, halved when the points come from a subpixel run.  A model that
+    // is none (iteration -1: all zeros) gives no matches.  Throws std::invalid_argument for a threshold that is not finite and
+    // positive and for what match() rejects.
+    std::vector<Match> match_guided(const std::vector<InterestPoint>& query, const std::vector<InterestPoint>& train, const Homography& model,
+                                    f32_t threshold = 3.0f, f32_t ratio = 0.8f, bool crossCheck = false, bool subpixel = false) {
+        return guided(query, train, SIFT_HIP_GUIDE_HOMOGRAPHY, model.h, threshold, ratio, crossCheck, subpixel);
+    }
+    std::vector<Match> match_guided(const std::vector<InterestPoint>& query, const std::vector<InterestPoint>& train, const Fundamental& model,
+                                    f32_t threshold = 3.0f, f32_t ratio = 0.8f, bool crossCheck = false, bool subpixel = false) {
+        return guided(query, train, SIFT_HIP_GUIDE_FUNDAMENTAL, model.f, threshold, ratio, crossCheck, subpixel);
     }
 
     // The geometric check of a match list (include/sift_hip.h, "geometric verification"): the best four-point homography
@@ -138,6 +140,57 @@ public:
     }
 
 private:
+    // both lists' descriptor rows and valid flags -> _desc, _kp
+    void rows(const std::vector<InterestPoint>& query, const std::vector<InterestPoint>& train) {
+        const size_t nq = query.size(), nt = train.size();
+        _desc.assign((nq + nt) * 128, 0.0f);
+        _kp.assign(nq + nt, sift_hip_keypoint{});
+        for (size_t i = 0; i < nq + nt; ++i) {
+            const InterestPoint& p = i < nq ? query[i] : train[i - nq];
+            if (p.descriptors.size() != 128) continue;
+            _kp[i].has_descriptor = 1;
+            for (size_t k = 0; k < 128; ++k) _desc[i * 128 + k] = p.descriptors[k];
+        }
+    }
+    std::vector<Match> records(size_t total) const {
+        std::vector<Match> out(total);
+        for (size_t i = 0; i < out.size(); ++i) {
+            out[i].query = _recs[i].query;
+            out[i].train = _recs[i].train;
+            out[i].dist2 = _recs[i].dist2;
+            out[i].second2 = _recs[i].second2;
+        }
+        return out;
+    }
+    std::vector<Match> guided(const std::vector<InterestPoint>& query, const std::vector<InterestPoint>& train, unsigned kind, const f32_t (&m)[9],
+                              f32_t threshold, f32_t ratio, bool crossCheck, bool subpixel) {
+        const size_t nq = query.size(), nt = train.size();
+        rows(query, train);
+        const f32_t scale = subpixel ? 0.5f : 1.0f;
+        _xy.resize((nq + nt) * 2);
+        for (size_t i = 0; i < nq + nt; ++i) {   // every point's image coordinates, as gather() forms them per match
+            const InterestPoint& p = i < nq ? query[i] : train[i - nq];
+            _xy[2 * i] = (f32_t)((unsigned)p.loc.x << p.octave) * scale;
+            _xy[2 * i + 1] = (f32_t)((unsigned)p.loc.y << p.octave) * scale;
+        }
+        const int64_t offsets[3] = {0, (int64_t)nq, (int64_t)(nq + nt)};
+        const int32_t pq = 0, pt = 1;
+        sift_hip_match_params prm{};
+        prm.ratio = ratio;
+        prm.cross_check = crossCheck ? 1 : 0;
+        sift_hip_guide_params guide{};
+        guide.model = kind;
+        guide.threshold = threshold;
+        _recs.resize(nq);
+        int32_t count = 0;
+        int64_t total = 0;
+        char err[512] = "";
+        const int rc = sift_hip_match_guided(_ctx, _desc.data(), _kp.data(), _xy.data(), 2, offsets, 1, &pq, &pt, &prm, &guide, m, _recs.data(), &count,
+                                             &total, err, sizeof(err));
+        if (rc == SIFT_HIP_EINVAL) throw std::invalid_argument(err);
+        if (rc != SIFT_HIP_OK) throw std::runtime_error(err);
+        return records((size_t)total);
+    }
     // the matches' image coordinates -> _pts, rows (qx, qy, tx, ty)
     void gather(const std::vector<InterestPoint>& query, const std::vector<InterestPoint>& train, const std::vector<Match>& matches, bool subpixel) {
         const f32_t scale = subpixel ? 0.5f : 1.0f;
@@ -158,6 +211,7 @@ private:
     std::vector<sift_hip_keypoint> _kp;
     std::vector<sift_hip_match_rec> _recs;
     std::vector<float> _pts;
+    std::vector<float> _xy;                // guided matching: both lists' image coordinates
 };
 
 }  // namespace sift

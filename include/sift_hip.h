@@ -361,6 +361,49 @@ int sift_hip_result_verify_fundamental(sift_hip_ctx* ctx, int n_pairs, const int
                                        sift_hip_match_rec* recs, int32_t* counts, int64_t* total, sift_hip_fundamental* models,
                                        uint8_t* inlier, char* err, int errlen);
 
+/* ---- guided matching: descriptor matching under a verified model (an extension) ----------------------------
+ * Everything of "descriptor matching" above holds unchanged - the fmaf chain, d2, the order (d2, index), validity, sets, pairs
+ * and the memory rules - with ONE more condition on a candidate.  Every pair p of a call carries a model kind (one per call),
+ * nine floats M_p, row-major, in the query-to-train convention of sift_hip_homography.h / sift_hip_fundamental.f, and a
+ * threshold in pixels; thr2 = threshold * threshold (one float product).  Every descriptor row has a point (x, y).  Train row j
+ * is ADMISSIBLE for query row i when the verification's own predicate holds, called as the RANSAC kernels call it:
+ *   homography   ransac_inlier(M_p, qx_i, qy_i, tx_j, ty_j, thr2)        (sift_amd/csrc/ransac_math.h)
+ *   fundamental  ransac_fund_inlier(M_p, qx_i, qy_i, tx_j, ty_j, thr2)   (sift_amd/csrc/ransac_fund_math.h)
+ *   candidates   a candidate (d2, j) takes part when it did before AND j is admissible for i.  The best and the second best are
+ *                the first two such candidates in the order (d2, j); the ratio test compares those two; a missing entry is
+ *                -1 / +inf as before.
+ *   cross-check  the reverse best of train row j is the first candidate in the order (d2, i) among the valid query rows i for
+ *                which j is admissible for i: the same model in the same direction, not its inverse.
+ *   no special   whatever the predicate says holds.  The all-zero model admits nothing (W > 0 and g > 0 are both false); a NaN
+ *   cases        or infinite coordinate makes its row admissible for nothing and by nothing; a pair whose verification found
+ *                no winner (its model is all zeros) therefore yields no records.  threshold * threshold may overflow to +inf:
+ *                then every finite row is admissible under a model with W > 0 / g > 0 there.
+ * The result does not depend on tile sizes, train splits or the launch shape; a plain host loop (hostmath_match_knn2_guided)
+ * checks every bit.  The admissibility test runs inside the matrix-instruction tile kernel: no nq x nt matrix is stored here
+ * either.
+ *
+ * Coordinates.  Generic calls: `xy`, two floats per descriptor row, parallel to `desc`, host or device memory.  Result call:
+ * per keypoint what sift_hip_result_verify gathers per record - (float)(x << octave), (float)(y << octave), times 0.5f when
+ * the last batch ran with subpixel - built on the GPU.  `models`: n_pairs x 9 floats, host or device memory.
+ * SIFT_HIP_EINVAL for an unknown model kind, a threshold that is not finite and > 0, NULL xy, models or guide, and for
+ * everything the unguided calls reject.  One launch of each kernel for all pairs of a call. */
+#define SIFT_HIP_GUIDE_HOMOGRAPHY 0
+#define SIFT_HIP_GUIDE_FUNDAMENTAL 1
+typedef struct sift_hip_guide_params {
+    uint32_t model;       /* SIFT_HIP_GUIDE_HOMOGRAPHY or SIFT_HIP_GUIDE_FUNDAMENTAL */
+    float threshold;      /* pixels, finite and > 0 */
+} sift_hip_guide_params;  /* 8 bytes */
+int sift_hip_knn2_guided(sift_hip_ctx* ctx, const float* desc, const sift_hip_keypoint* kp, const float* xy, int n_sets,
+                         const int64_t* offsets, int n_pairs, const int32_t* pair_q, const int32_t* pair_t,
+                         const sift_hip_guide_params* guide, const float* models, int32_t* idx, float* dist2, char* err, int errlen);
+int sift_hip_match_guided(sift_hip_ctx* ctx, const float* desc, const sift_hip_keypoint* kp, const float* xy, int n_sets,
+                          const int64_t* offsets, int n_pairs, const int32_t* pair_q, const int32_t* pair_t,
+                          const sift_hip_match_params* match_params, const sift_hip_guide_params* guide, const float* models,
+                          sift_hip_match_rec* recs, int32_t* counts, int64_t* total, char* err, int errlen);
+int sift_hip_result_match_guided(sift_hip_ctx* ctx, int n_pairs, const int32_t* pair_q, const int32_t* pair_t,
+                                 const sift_hip_match_params* match_params, const sift_hip_guide_params* guide, const float* models,
+                                 sift_hip_match_rec* recs, int32_t* counts, int64_t* total, char* err, int errlen);
+
 /* ---- inspection of the last batch (parity tests) ------------------------------------------------ */
 /* kind: 0 gaussian (levels 0..D), 1 dog (0..D-1), 2 magnitude, 3 orientation (initial gradient
  * maps, sift.cpp:130-160, only for levels some keypoint scale selects; 0x0 otherwise). */

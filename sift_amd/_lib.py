@@ -38,6 +38,7 @@ SYMBOLS = [
     "sift_hip_knn2", "sift_hip_match", "sift_hip_result_match",
     "sift_hip_ransac_homography", "sift_hip_result_verify", "sift_hip_refine_homography",
     "sift_hip_ransac_fundamental", "sift_hip_result_verify_fundamental",
+    "sift_hip_knn2_guided", "sift_hip_match_guided", "sift_hip_result_match_guided",
 ]
 
 
@@ -49,6 +50,12 @@ class Params(C.Structure):
 class MatchParams(C.Structure):
     _fields_ = [("ratio", C.c_float), ("cross_check", C.c_uint8), ("reserved", C.c_uint8 * 3)]
 
+
+class GuideParams(C.Structure):
+    _fields_ = [("model", C.c_uint32), ("threshold", C.c_float)]
+
+
+GUIDE_MODELS = {"homography": 0, "fundamental": 1}
 
 MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("dist2", "<f4"), ("second2", "<f4")])
 assert MATCH_DTYPE.itemsize == 16
@@ -201,5 +208,11 @@ def load():
                                          vp, vp, cs, ci]
     L.sift_hip_ransac_fundamental.argtypes = L.sift_hip_ransac_homography.argtypes
     L.sift_hip_result_verify_fundamental.argtypes = L.sift_hip_result_verify.argtypes
+    # xy and models may be host or device memory as well
+    gp = C.POINTER(GuideParams)
+    L.sift_hip_knn2_guided.argtypes = [vp, vp, vp, vp, ci, i64p, ci, i32p, i32p, gp, vp, vp, vp, cs, ci]
+    L.sift_hip_match_guided.argtypes = [vp, vp, vp, vp, ci, i64p, ci, i32p, i32p, C.POINTER(MatchParams), gp, vp, vp, i32p,
+                                        C.POINTER(C.c_int64), cs, ci]
+    L.sift_hip_result_match_guided.argtypes = [vp, ci, i32p, i32p, C.POINTER(MatchParams), gp, vp, vp, i32p, C.POINTER(C.c_int64), cs, ci]
     _lib = L
     return L

@@ -4,6 +4,7 @@ overlay :59-76) on top of the GPU path — SURVEY.md §8(f) rows 1-3.
     python -m sift_amd.cli -i image.pgm [-s 1.6] [-k 1.41421354] [-o 4] [-d 3] [-p 0] [-r 1]
     python -m sift_amd.cli -i a.pgm --match b.pgm [--ratio 0.8] [--cross-check]      (an extension: matches.txt)
     python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--iterations 2048] [--threshold 3] [--seed 0] [--refine 0] [--model homography|fundamental]   (... and inliers.txt)
+    python -m sift_amd.cli -i a.pgm --match b.pgm --verify --guided [--guided-ratio R]   (... and guided.txt: the matches again, under the verified model)
 
 Image ingest follows Vigra's scalar import: band 0 of multi-band files, values unscaled.  PGM,
 PPM, PNG and JPEG are decoded by the library itself (sift_amd/csrc/image_io.cpp, jpeg_decode.cpp: no PIL, no OpenCV, no libjpeg).
@@ -140,9 +141,17 @@ def main(argv=None) -> int:
     ap.add_argument("--model", choices=("homography", "fundamental"), default="homography",
                     help="model of --verify: a four-point homography (a plane or a rotating camera), or a seven-point fundamental matrix "
                          "(two views of a general scene)")
+    ap.add_argument("--guided", action="store_true",
+                    help="with --verify: match again under the winning model (a point competes only within --threshold pixels of it); "
+                         "the matches go to guided.txt")
+    ap.add_argument("--guided-ratio", type=float, default=None, help="ratio test of --guided (default: --ratio)")
     args = ap.parse_args(argv)
     if args.verify and not args.match:
         ap.error("--verify needs --match")
+    if args.guided and not args.verify:
+        ap.error("--guided needs --verify")
+    if args.guided_ratio is not None and not args.guided:
+        ap.error("--guided-ratio needs --guided")
     if args.model != "homography" and not args.verify:
         ap.error("--model needs --verify")
     if args.refine and args.model == "fundamental":
@@ -189,6 +198,11 @@ def main(argv=None) -> int:
                 else:
                     for r in range(3):
                         print("H " + " ".join("%.9g" % float(v) for v in model["h"][3 * r:3 * r + 3]))
+                if args.guided:   # no winner: the all-zero model admits nothing, the file is empty
+                    ratio = args.ratio if args.guided_ratio is None else args.guided_ratio
+                    guided = sift.match_guided(points, points2, model, args.threshold, ratio, args.cross_check)
+                    write_matches("guided.txt", guided)
+                    print(f"{len(guided)} guided matches -> guided.txt")
     except (PreconditionViolation, AssertionError, RuntimeError, OSError) as ex:  # main.cpp:90-92
         print(ex, file=sys.stderr)
     return 0

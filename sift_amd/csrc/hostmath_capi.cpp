@@ -112,6 +112,51 @@ void hostmath_match_knn2(const float* q, const uint8_t* q_valid, long long nq, c
     }
     delete[] tn;
 }
+// Guided matching as include/sift_hip.h defines it, in plain loops: hostmath_match_knn2 with one more condition on a candidate,
+// the verification's predicate under the model m (nine floats; model 0: ransac_inlier, 1: ransac_fund_inlier) between the query
+// row's point and the train row's.  q_xy / t_xy: two floats per row.  reverse 0: idx / dist2 are nq x 2, the top-2 train rows of
+// every query row.  reverse 1: they are nt x 2, the top-2 QUERY rows of every train row under the same predicate with the same
+// arguments - the cross-check's reverse best.
+void hostmath_match_knn2_guided(const float* q, const uint8_t* q_valid, const float* q_xy, long long nq, const float* t, const uint8_t* t_valid,
+                                const float* t_xy, long long nt, int model, const float* m, float threshold, int reverse, int32_t* idx,
+                                float* dist2) {
+    float mm[9];
+    for (int k = 0; k < 9; ++k) mm[k] = m[k];
+    const float thr2 = threshold * threshold;
+    const float* own = reverse ? t : q;                 // the rows that get an entry, and the rows they choose among
+    const float* other = reverse ? q : t;
+    const uint8_t* own_valid = reverse ? t_valid : q_valid;
+    const uint8_t* other_valid = reverse ? q_valid : t_valid;
+    const long long n_own = reverse ? nt : nq, n_other = reverse ? nq : nt;
+    float* on = new float[n_other > 0 ? n_other : 1];
+    for (long long j = 0; j < n_other; ++j) on[j] = match_dot(other + j * 128, other + j * 128);
+    for (long long i = 0; i < n_own; ++i) {
+        float d1 = INFINITY, d2 = INFINITY;
+        int32_t i1 = -1, i2 = -1;
+        if (!own_valid || own_valid[i]) {
+            const float na = match_dot(own + i * 128, own + i * 128);
+            for (long long j = 0; j < n_other; ++j) {
+                if (other_valid && !other_valid[j]) continue;
+                const long long qi = reverse ? j : i, tj = reverse ? i : j;
+                const bool adm = model == 1 ? sift_hip::ransac_fund_inlier(mm, q_xy[2 * qi], q_xy[2 * qi + 1], t_xy[2 * tj], t_xy[2 * tj + 1], thr2)
+                                            : sift_hip::ransac_inlier(mm, q_xy[2 * qi], q_xy[2 * qi + 1], t_xy[2 * tj], t_xy[2 * tj + 1], thr2);
+                if (!adm) continue;
+                const float s = na + on[j];
+                const float v = s - 2.0f * match_dot(own + i * 128, other + j * 128);
+                const float d = (v < 0.0f) ? 0.0f : v;
+                if (d != d) continue;
+                if (i1 < 0 || d < d1) {
+                    d2 = d1; i2 = i1; d1 = d; i1 = (int32_t)j;
+                } else if (i2 < 0 || d < d2) {
+                    d2 = d; i2 = (int32_t)j;
+                }
+            }
+        }
+        idx[2 * i] = i1; idx[2 * i + 1] = i2;
+        dist2[2 * i] = d1; dist2[2 * i + 1] = d2;
+    }
+    delete[] on;
+}
 // RANSAC homography as ransac_math.h defines it, in plain loops: what sift_hip_ransac_homography must reproduce bit for bit.
 void hostmath_ransac_draw(uint32_t seed, uint32_t set, uint32_t iteration, uint32_t m, uint32_t* idx) {
     uint32_t d[4];

@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "match_kernels.h"
+#include "ransac_fund_math.h"   // ransac_inlier, ransac_fund_inlier: the guided instantiations' admissibility test
 
 namespace sift_hip {
 
@@ -49,6 +50,25 @@ __device__ __forceinline__ void store_row4(float* row, int c4, f4v v) {
     *reinterpret_cast<f2v*>(row + 64 + 2 * c4) = o;
 }
 
+// The guide of a tile kernel instantiation (include/sift_hip.h, "guided matching"): none, or one of the two verification
+// predicates, called with the arguments the RANSAC kernels give them.
+struct NoGuide {
+    static constexpr bool kOn = false;
+    static __device__ __forceinline__ bool admissible(const float (&)[9], float, float, float, float, float) { return true; }
+};
+struct HomographyGuide {
+    static constexpr bool kOn = true;
+    static __device__ __forceinline__ bool admissible(const float (&m)[9], float qx, float qy, float tx, float ty, float thr2) {
+        return ransac_inlier(m, qx, qy, tx, ty, thr2);
+    }
+};
+struct FundamentalGuide {
+    static constexpr bool kOn = true;
+    static __device__ __forceinline__ bool admissible(const float (&m)[9], float qx, float qy, float tx, float ty, float thr2) {
+        return ransac_fund_inlier(m, qx, qy, tx, ty, thr2);
+    }
+};
+
 }  // namespace
 
 // n(a) = dot(a, a) as the chain, and the row's valid flag.  64 rows per workgroup: fetched coalesced into LDS (129 floats a row:
@@ -70,13 +90,22 @@ __global__ __launch_bounds__(256) void match_norm_kernel(const float* __restrict
     }
 }
 
+// Guide::kOn: a candidate also has to be admissible under its pair's model.  The stage's train coordinates travel with its norms
+// and flags; the lane's own point stays in two registers, the tile's model and direction are wave-uniform.  In a tile of the
+// cross-check (direction 1) the lane holds a train row and the stage's rows are query rows: the predicate's arguments keep their
+// meaning, so the two points change places, not the model.  Admissibility does not depend on the products: a lane forms the 32
+// bits of its stage rows two at a time behind each group of eight matrix instructions, and the epilogue's ballot asks for an
+// admissible candidate - under a narrow band nearly every element is skipped although the lane's second best is still +inf.
+// (Little of that arithmetic runs under the products yet: DESIGN.md 3d has the cost and what was tried.)
+template <class Guide>
 __global__ __launch_bounds__(256) void match_tile_kernel(const float* __restrict__ desc, const float* __restrict__ norm,
                                                          const uint8_t* __restrict__ valid, const MatchTile* __restrict__ tiles,
-                                                         MatchTop2* __restrict__ part) {
+                                                         MatchTop2* __restrict__ part, MatchGuideArgs ga) {
     __shared__ __attribute__((aligned(16))) float sq[kMatchQ * kRowStride];
     __shared__ __attribute__((aligned(16))) float st[2][kMatchT * kRowStride];
     __shared__ __attribute__((aligned(16))) float stn[2][kMatchT];
     __shared__ __attribute__((aligned(16))) unsigned char stv[2][kMatchT];
+    __shared__ __attribute__((aligned(16))) float stxy[2][Guide::kOn ? 2 * kMatchT : 4];   // (x, y) of the stage's rows
 
     struct { int q_row0, q_rows, t_set0, t_lo, t_hi; } tl;   // wave-uniform: scalar registers
     tl.q_row0 = tiles[blockIdx.x].q_row0; tl.q_rows = tiles[blockIdx.x].q_rows; tl.t_set0 = tiles[blockIdx.x].t_set0;
@@ -93,11 +122,25 @@ __global__ __launch_bounds__(256) void match_tile_kernel(const float* __restrict
     }
     const int my_q = w * 32 + c;
     const float nq = my_q < tl.q_rows ? norm[tl.q_row0 + my_q] : 0.0f;
+    float gm[9] = {};        // the tile's model (scalar registers)
+    bool swapped = false;    // a tile of the cross-check: the lane's row is the train row of the predicate
+    float lx = 0.0f, ly = 0.0f;
+    if constexpr (Guide::kOn) {
+        const int pd = tiles[blockIdx.x].pair_dir;
+        swapped = (pd & 1) != 0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) gm[k] = ga.models[9 * (size_t)(pd >> 1) + k];
+        if (my_q < tl.q_rows) {
+            lx = ga.xy[2 * (size_t)(tl.q_row0 + my_q)];
+            ly = ga.xy[2 * (size_t)(tl.q_row0 + my_q) + 1];
+        }
+    }
 
     const int n_stages = (tl.t_hi - tl.t_lo + kMatchT - 1) / kMatchT;
     f4v pre[8];            // the next stage's rows on their way from memory: fetched before this stage's products, stored after
     float pre_n = 0.0f;
     int pre_v = 0;
+    f2v pre_xy = {0.0f, 0.0f};
     auto fetch = [&](int stage) {
         const int t0 = tl.t_lo + stage * kMatchT;
 #pragma unroll
@@ -110,6 +153,10 @@ __global__ __launch_bounds__(256) void match_tile_kernel(const float* __restrict
             const bool in = t0 + tid < tl.t_hi;      // rows past the range are masked by index, like invalid ones
             pre_n = in ? norm[tl.t_set0 + t0 + tid] : 0.0f;
             pre_v = in ? (int)valid[tl.t_set0 + t0 + tid] : 0;
+            if constexpr (Guide::kOn) {
+                pre_xy.x = in ? ga.xy[2 * (size_t)(tl.t_set0 + t0 + tid)] : 0.0f;
+                pre_xy.y = in ? ga.xy[2 * (size_t)(tl.t_set0 + t0 + tid) + 1] : 0.0f;
+            }
         }
     };
     auto stash = [&](int buf) {
@@ -121,6 +168,7 @@ __global__ __launch_bounds__(256) void match_tile_kernel(const float* __restrict
         if (tid < kMatchT) {
             stn[buf][tid] = pre_n;
             stv[buf][tid] = (unsigned char)pre_v;
+            if constexpr (Guide::kOn) *reinterpret_cast<f2v*>(&stxy[buf][2 * tid]) = pre_xy;
         }
     };
 
@@ -149,6 +197,16 @@ __global__ __launch_bounds__(256) void match_tile_kernel(const float* __restrict
             tn[g] = *reinterpret_cast<const f4v*>(&stn[buf][tr0]);
             tv[g] = *reinterpret_cast<const unsigned*>(&stv[buf][tr0]);
         }
+        // guided: the coordinates of the same rows, two consecutive rows per read - result elements 2 m and 2 m + 1 of the 32
+        f4v cxy[Guide::kOn ? 16 : 1];
+        unsigned adm = 0u;   // bit 16 half + r: the row of result element r of that half is admissible
+        if constexpr (Guide::kOn) {
+#pragma unroll
+            for (int m = 0; m < 16; ++m) {
+                const int r = 2 * (m & 7), tr0 = (m >> 3) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                cxy[m] = *reinterpret_cast<const f4v*>(&stxy[buf][2 * tr0]);
+            }
+        }
         f16v acc0, acc1;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc0[r] = 0.0f; acc1[r] = 0.0f; }
@@ -172,6 +230,17 @@ __global__ __launch_bounds__(256) void match_tile_kernel(const float* __restrict
                 acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[cur][e], b[cur][e], acc0, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[cur][e], b[cur][e], acc1, 0, 0, 0);
             }
+            if constexpr (Guide::kOn) {
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const float ex = u ? cxy[m].z : cxy[m].x, ey = u ? cxy[m].w : cxy[m].y;
+                    // the direction is wave-uniform: a branch, and in each arm the predicate has its arguments in their places,
+                    // so what depends on the lane's own point alone is one computation for all calls - the same roundings
+                    const bool ok = swapped ? Guide::admissible(gm, ex, ey, lx, ly, ga.thr2) : Guide::admissible(gm, lx, ly, ex, ey, ga.thr2);
+                    adm |= ok ? (1u << (2 * m + u)) : 0u;
+                }
+                asm volatile("" : "+v"(adm));   // the two bits are formed here, behind this group's products, not in the epilogue
+            }
             __builtin_amdgcn_sched_barrier(0);   // ... and are not moved behind them
         }
         // result element r of lane (c, h): train row (r & 3) + 8 (r >> 2) + 4 h of the half, query row c of the wave's 32.
@@ -187,9 +256,12 @@ __global__ __launch_bounds__(256) void match_tile_kernel(const float* __restrict
                 const float dot = half ? acc1[r] : acc0[r];
                 const float sum = nq + tn[half * 4 + (r >> 2)][r & 3];
                 float v = sum - 2.0f * dot;
-                if (__builtin_amdgcn_ballot_w64(!(v > d2)) != 0) {
+                bool cand = !(v > d2);
+                if constexpr (Guide::kOn) cand &= ((adm >> (16 * half + r)) & 1u) != 0;
+                if (__builtin_amdgcn_ballot_w64(cand) != 0) {
                     v = (v < 0.0f) ? 0.0f : v;
-                    const bool row_ok = ((tv[half * 4 + (r >> 2)] >> (8 * (r & 3))) & 0xffu) != 0;
+                    bool row_ok = ((tv[half * 4 + (r >> 2)] >> (8 * (r & 3))) & 0xffu) != 0;
+                    if constexpr (Guide::kOn) row_ok &= ((adm >> (16 * half + r)) & 1u) != 0;
                     top2_insert(row_ok & (v == v), v, jbase + tr, d1, i1, d2, i2);
                 }
             }
@@ -208,6 +280,18 @@ __global__ __launch_bounds__(256) void match_tile_kernel(const float* __restrict
         o.d1 = d1; o.d2 = d2; o.i1 = i1; o.i2 = i2;
         part[(size_t)blockIdx.x * kMatchQ + my_q] = o;
     }
+}
+
+// the image coordinates of every keypoint record, as sift_hip_result_verify gathers them per match: (float)(x << octave) * scale
+__global__ __launch_bounds__(256) void match_coords_kernel(const sift_hip_keypoint* __restrict__ kp, long long rows, float coord_scale,
+                                                           float* __restrict__ xy) {
+    const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (row >= rows) return;
+    const sift_hip_keypoint k = kp[row];
+    f2v o;
+    o.x = (float)((uint32_t)k.x << k.octave) * coord_scale;
+    o.y = (float)((uint32_t)k.y << k.octave) * coord_scale;
+    *reinterpret_cast<f2v*>(xy + 2 * (size_t)row) = o;
 }
 
 // the partial top-2s of a block's tiles -> its rows of the result, by the same order; an invalid query row has no entry
@@ -295,7 +379,19 @@ void launch_match_norms(hipStream_t s, const float* d_desc, const sift_hip_keypo
 void launch_match_tiles(hipStream_t s, const float* d_desc, const float* d_norm, const uint8_t* d_valid, const MatchTile* d_tiles,
                         int n_tiles, MatchTop2* d_part) {
     if (n_tiles <= 0) return;
-    hipLaunchKernelGGL(match_tile_kernel, dim3((unsigned)n_tiles), dim3(256), 0, s, d_desc, d_norm, d_valid, d_tiles, d_part);
+    hipLaunchKernelGGL(match_tile_kernel<NoGuide>, dim3((unsigned)n_tiles), dim3(256), 0, s, d_desc, d_norm, d_valid, d_tiles, d_part, MatchGuideArgs{});
+}
+void launch_match_tiles_guided(hipStream_t s, const float* d_desc, const float* d_norm, const uint8_t* d_valid, const MatchTile* d_tiles,
+                               int n_tiles, MatchTop2* d_part, int model, const MatchGuideArgs& ga) {
+    if (n_tiles <= 0) return;
+    if (model == SIFT_HIP_GUIDE_FUNDAMENTAL)
+        hipLaunchKernelGGL(match_tile_kernel<FundamentalGuide>, dim3((unsigned)n_tiles), dim3(256), 0, s, d_desc, d_norm, d_valid, d_tiles, d_part, ga);
+    else
+        hipLaunchKernelGGL(match_tile_kernel<HomographyGuide>, dim3((unsigned)n_tiles), dim3(256), 0, s, d_desc, d_norm, d_valid, d_tiles, d_part, ga);
+}
+void launch_match_coords(hipStream_t s, const sift_hip_keypoint* d_kp, long long rows, float coord_scale, float* d_xy) {
+    if (rows <= 0) return;
+    hipLaunchKernelGGL(match_coords_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, d_kp, rows, coord_scale, d_xy);
 }
 void launch_match_merge(hipStream_t s, const MatchTop2* d_part, const uint8_t* d_valid, const MatchBlock* d_blocks, int n_blocks,
                         int32_t* d_idx, float* d_dist) {

@@ -1,7 +1,9 @@
-// Host side of descriptor matching (include/sift_hip.h: sift_hip_knn2, sift_hip_match, sift_hip_result_match): staging of
+// Host side of descriptor matching (include/sift_hip.h: sift_hip_knn2, sift_hip_match, sift_hip_result_match, and their guided
+// counterparts sift_hip_knn2_guided, sift_hip_match_guided, sift_hip_result_match_guided): staging of
 // caller memory, the tile table that makes many pairs one launch, and the scratch memory, which the first match call of a
 // context allocates and the context keeps - outside the batch arena, so a context that never matches allocates nothing here.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -19,6 +21,7 @@ struct MatchState {
     ScratchBuf d_part;                       // partial top-2s, kMatchQ per tile
     ScratchBuf d_idx, d_dist;                // top-2 of every query row (forward rows first, then the cross-check's reverse rows)
     ScratchBuf d_seg, d_out, d_counts;       // records per pair segment, the dense list, per-pair counts
+    ScratchBuf d_xy, d_models;               // guided matching: the rows' points (staged, or built from the keypoints), the pairs' models
     void* h_tables = nullptr;         // page-locked image of the three tables (the copy is asynchronous)
     size_t h_cap = 0;
     std::vector<int32_t> counts;
@@ -27,7 +30,7 @@ struct MatchState {
 void match_state_free(MatchState* st) {
     if (!st) return;
     for (ScratchBuf* b : {&st->d_desc, &st->d_kp, &st->d_norm, &st->d_valid, &st->d_tiles, &st->d_blocks, &st->d_pairs, &st->d_part, &st->d_idx,
-                   &st->d_dist, &st->d_seg, &st->d_out, &st->d_counts})
+                   &st->d_dist, &st->d_seg, &st->d_out, &st->d_counts, &st->d_xy, &st->d_models})
         b->release();
     if (st->h_tables) {
         ApiGuard api;
@@ -58,6 +61,12 @@ struct Job {
     // sift_hip_result_verify goes on with the list where it is: the dense records on the device, the pairs' counts (both null: not asked)
     const sift_hip_match_rec** d_recs_out = nullptr;
     int32_t* host_counts_out = nullptr;
+    // guided matching (guided: all three must be given, except that sift_hip_result_match_guided builds xy from the keypoints)
+    bool guided = false;
+    const float* xy = nullptr;
+    const sift_hip_guide_params* guide = nullptr;
+    const float* models = nullptr;
+    float coord_scale = 1.0f;   // the result call's: 0.5f after a batch with subpixel
 };
 
 int fail(const Job& j, const char* msg) {
@@ -68,8 +77,8 @@ int fail(const Job& j, const char* msg) {
 size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // the tiles of one (query set, train set): blocks of kMatchQ query rows, each against `splits` ranges of the train set
-void add_tiles(long long q0, long long nq, long long t0, long long nt, int target_tiles_per_block, int out_row0, std::vector<MatchTile>& tiles,
-               std::vector<MatchBlock>& blocks) {
+void add_tiles(long long q0, long long nq, long long t0, long long nt, int target_tiles_per_block, int out_row0, int pair_dir,
+               std::vector<MatchTile>& tiles, std::vector<MatchBlock>& blocks) {
     const long long stages = (nt + kMatchT - 1) / kMatchT;
     const long long stages_per_split_min = kMatchSplitRows / kMatchT;
     long long splits = std::max<long long>(1, std::min<long long>(target_tiles_per_block, (nt + kMatchSplitRows - 1) / kMatchSplitRows));
@@ -88,6 +97,7 @@ void add_tiles(long long q0, long long nq, long long t0, long long nt, int targe
             t.t_set0 = (int)t0;
             t.t_lo = (int)(s0 * kMatchT);
             t.t_hi = (int)std::min<long long>(nt, (s0 + per) * kMatchT);
+            t.pair_dir = pair_dir;
             tiles.push_back(t);
         }
         blk.n_tiles = (int)tiles.size() - blk.first_tile;
@@ -117,6 +127,15 @@ int run(void* arg) {
         use_ratio = r != 0.0f;
         ratio2 = r * r;
         cross = j.params->cross_check != 0;
+    }
+    if (j.guided) {
+        if (!j.guide) return fail(j, "sift_hip match: no guide parameters");
+        if (j.guide->model != SIFT_HIP_GUIDE_HOMOGRAPHY && j.guide->model != SIFT_HIP_GUIDE_FUNDAMENTAL)
+            return fail(j, "sift_hip match: guide model must be 0 (homography) or 1 (fundamental)");
+        if (!(std::isfinite(j.guide->threshold) && j.guide->threshold > 0.0f)) return fail(j, "sift_hip match: guide threshold must be finite and > 0");
+        if (!j.models) return fail(j, "sift_hip match: no models");
+        if (!j.xy && !j.inputs_on_device) return fail(j, "sift_hip match: no coordinates");
+        if (j.n_pairs > 0x3fffffff) return fail(j, "sift_hip match: too many pairs");
     }
     long long fwd_rows = 0, rev_rows = 0;
     for (int p = 0; p < j.n_pairs; ++p) {
@@ -153,6 +172,30 @@ int run(void* arg) {
             d_kp = st.d_kp.as<sift_hip_keypoint>();
         }
     }
+    MatchGuideArgs ga;
+    if (j.guided) {
+        ga.thr2 = j.guide->threshold * j.guide->threshold;
+        ga.xy = j.xy;
+        if (j.inputs_on_device) {   // the context's keypoints: every row's point is built on the device
+            st.d_xy.ensure((size_t)rows * 2 * sizeof(float));
+            launch_match_coords(v.stream, d_kp, rows, j.coord_scale, st.d_xy.as<float>());
+            ga.xy = st.d_xy.as<float>();
+        } else if (!match_ptr_on_device(j.xy)) {
+            match_wait(j.c);   // the staging buffers may still hold the keypoints
+            st.d_xy.ensure((size_t)rows * 2 * sizeof(float));
+            match_upload(j.c, st.d_xy.p, j.xy, (size_t)rows * 2 * sizeof(float));
+            match_wait(j.c);
+            ga.xy = st.d_xy.as<float>();
+        }
+        ga.models = j.models;
+        if (!match_ptr_on_device(j.models)) {
+            match_wait(j.c);
+            st.d_models.ensure((size_t)j.n_pairs * 9 * sizeof(float));
+            match_upload(j.c, st.d_models.p, j.models, (size_t)j.n_pairs * 9 * sizeof(float));
+            match_wait(j.c);
+            ga.models = st.d_models.as<float>();
+        }
+    }
 
     // ---- the tables: every pair's tiles (and, for the cross-check, those of the pair with its roles swapped) ----
     long long q_blocks = 0;
@@ -172,10 +215,10 @@ int run(void* arg) {
         const long long q0 = j.offsets[j.pair_q[p]], nq = j.offsets[j.pair_q[p] + 1] - q0;
         const long long t0 = j.offsets[j.pair_t[p]], nt = j.offsets[j.pair_t[p] + 1] - t0;
         pairs[(size_t)p] = MatchPair{(int)out_row, (int)nq, cross ? (int)rev_row : -1, 0};
-        add_tiles(q0, nq, t0, nt, per_block, (int)out_row, tiles, blocks);
+        add_tiles(q0, nq, t0, nt, per_block, (int)out_row, j.guided ? 2 * p : 0, tiles, blocks);
         out_row += nq;
         if (cross) {
-            add_tiles(t0, nt, q0, nq, per_block, (int)rev_row, tiles, blocks);
+            add_tiles(t0, nt, q0, nq, per_block, (int)rev_row, j.guided ? 2 * p + 1 : 0, tiles, blocks);
             rev_row += nt;
         }
     }
@@ -213,8 +256,12 @@ int run(void* arg) {
 
     // ---- the launches: one of each kernel, whatever the number of pairs ----
     launch_match_norms(v.stream, d_desc, d_kp, rows, st.d_norm.as<float>(), st.d_valid.as<uint8_t>());
-    launch_match_tiles(v.stream, d_desc, st.d_norm.as<float>(), st.d_valid.as<uint8_t>(), st.d_tiles.as<MatchTile>(), (int)tiles.size(),
-                       st.d_part.as<MatchTop2>());
+    if (j.guided)
+        launch_match_tiles_guided(v.stream, d_desc, st.d_norm.as<float>(), st.d_valid.as<uint8_t>(), st.d_tiles.as<MatchTile>(), (int)tiles.size(),
+                                  st.d_part.as<MatchTop2>(), (int)j.guide->model, ga);
+    else
+        launch_match_tiles(v.stream, d_desc, st.d_norm.as<float>(), st.d_valid.as<uint8_t>(), st.d_tiles.as<MatchTile>(), (int)tiles.size(),
+                           st.d_part.as<MatchTop2>());
     launch_match_merge(v.stream, st.d_part.as<MatchTop2>(), st.d_valid.as<uint8_t>(), st.d_blocks.as<MatchBlock>(), (int)blocks.size(), d_idx,
                        d_dist);
     SIFT_HIP_CHECK(hipGetLastError());
@@ -268,6 +315,26 @@ int match_result_on_device(sift_hip_ctx* c, const char* who, int n_pairs, const 
 }
 }  // namespace sift_hip
 
+// sift_hip_result_match_guided: the images' rows of the device-resident results, their points built from the keypoints
+static int result_match_guided(sift_hip_ctx* c, int n_pairs, const int32_t* pair_q, const int32_t* pair_t, const sift_hip_match_params* params,
+                               const sift_hip_guide_params* guide, const float* models, sift_hip_match_rec* recs, int32_t* counts, int64_t* total,
+                               char* err, int errlen) {
+    using namespace sift_hip;
+    const MatchCtxView v = match_ctx_view(c);
+    if (!v.have_result) {
+        match_set_err(err, errlen, "sift_hip_result_match_guided: the context holds no results");
+        return SIFT_HIP_EINVAL;
+    }
+    std::vector<int64_t> offsets((size_t)v.n_images + 1, 0);
+    for (int i = 0; i < v.n_images; ++i) offsets[(size_t)i + 1] = offsets[(size_t)i] + v.counts[i];
+    Job j{c, v.d_desc, v.d_kp, true, v.n_images, offsets.data(), n_pairs, pair_q, pair_t, params, nullptr, nullptr, recs, counts, total, err, errlen};
+    j.guided = true;
+    j.guide = guide;
+    j.models = models;
+    j.coord_scale = ransac_ctx_subpixel(c) ? 0.5f : 1.0f;
+    return match_guarded(err, errlen, run, &j);
+}
+
 using namespace sift_hip;
 
 extern "C" {
@@ -293,6 +360,40 @@ int sift_hip_result_match(sift_hip_ctx* c, int n_pairs, const int32_t* pair_q, c
     if (!c) { match_set_err(err, errlen, "sift_hip_result_match: no context (matching runs on the GPU only)"); return SIFT_HIP_EINVAL; }
     if (!params) { match_set_err(err, errlen, "sift_hip_result_match: no parameters"); return SIFT_HIP_EINVAL; }
     return match_result_on_device(c, "sift_hip_result_match", n_pairs, pair_q, pair_t, params, recs, counts, total, nullptr, nullptr, err, errlen);
+}
+
+int sift_hip_knn2_guided(sift_hip_ctx* c, const float* desc, const sift_hip_keypoint* kp, const float* xy, int n_sets, const int64_t* offsets,
+                         int n_pairs, const int32_t* pair_q, const int32_t* pair_t, const sift_hip_guide_params* guide, const float* models,
+                         int32_t* idx, float* dist2, char* err, int errlen) {
+    if (!c) { match_set_err(err, errlen, "sift_hip_knn2_guided: no context (matching runs on the GPU only)"); return SIFT_HIP_EINVAL; }
+    Job j{c, desc, kp, false, n_sets, offsets, n_pairs, pair_q, pair_t, nullptr, idx, dist2, nullptr, nullptr, nullptr, err, errlen};
+    j.guided = true;
+    j.xy = xy;
+    j.guide = guide;
+    j.models = models;
+    return match_guarded(err, errlen, run, &j);
+}
+
+int sift_hip_match_guided(sift_hip_ctx* c, const float* desc, const sift_hip_keypoint* kp, const float* xy, int n_sets, const int64_t* offsets,
+                          int n_pairs, const int32_t* pair_q, const int32_t* pair_t, const sift_hip_match_params* params,
+                          const sift_hip_guide_params* guide, const float* models, sift_hip_match_rec* recs, int32_t* counts, int64_t* total,
+                          char* err, int errlen) {
+    if (!c) { match_set_err(err, errlen, "sift_hip_match_guided: no context (matching runs on the GPU only)"); return SIFT_HIP_EINVAL; }
+    if (!params) { match_set_err(err, errlen, "sift_hip_match_guided: no parameters"); return SIFT_HIP_EINVAL; }
+    Job j{c, desc, kp, false, n_sets, offsets, n_pairs, pair_q, pair_t, params, nullptr, nullptr, recs, counts, total, err, errlen};
+    j.guided = true;
+    j.xy = xy;
+    j.guide = guide;
+    j.models = models;
+    return match_guarded(err, errlen, run, &j);
+}
+
+int sift_hip_result_match_guided(sift_hip_ctx* c, int n_pairs, const int32_t* pair_q, const int32_t* pair_t, const sift_hip_match_params* params,
+                                 const sift_hip_guide_params* guide, const float* models, sift_hip_match_rec* recs, int32_t* counts,
+                                 int64_t* total, char* err, int errlen) {
+    if (!c) { match_set_err(err, errlen, "sift_hip_result_match_guided: no context (matching runs on the GPU only)"); return SIFT_HIP_EINVAL; }
+    if (!params) { match_set_err(err, errlen, "sift_hip_result_match_guided: no parameters"); return SIFT_HIP_EINVAL; }
+    return result_match_guided(c, n_pairs, pair_q, pair_t, params, guide, models, recs, counts, total, err, errlen);
 }
 
 }  // extern "C"

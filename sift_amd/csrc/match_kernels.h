@@ -17,7 +17,13 @@ struct MatchTile {
     int q_row0, q_rows;   // first query row (row of the descriptor array), rows of the block (<= kMatchQ)
     int t_set0;           // first row of the train set
     int t_lo, t_hi;       // train rows [t_lo, t_hi) of the set, t_lo a multiple of kMatchT
-    int pad;
+    int pair_dir;         // guided matching: 2 * pair + direction (1: a tile of the cross-check, roles swapped); else 0
+};
+// what the guided instantiations of the tile kernel read besides: (x, y) of every descriptor row, nine floats per pair, threshold^2
+struct MatchGuideArgs {
+    const float* xy = nullptr;
+    const float* models = nullptr;
+    float thr2 = 0.0f;
 };
 // one block of query rows of one pair: its partial top-2s (tiles first_tile .. + n_tiles) become rows of the result
 struct MatchBlock {
@@ -38,6 +44,11 @@ struct MatchPair {
 void launch_match_norms(hipStream_t s, const float* d_desc, const sift_hip_keypoint* d_kp, long long rows, float* d_norm, uint8_t* d_valid);
 void launch_match_tiles(hipStream_t s, const float* d_desc, const float* d_norm, const uint8_t* d_valid, const MatchTile* d_tiles,
                         int n_tiles, MatchTop2* d_part);
+// model: SIFT_HIP_GUIDE_HOMOGRAPHY or SIFT_HIP_GUIDE_FUNDAMENTAL
+void launch_match_tiles_guided(hipStream_t s, const float* d_desc, const float* d_norm, const uint8_t* d_valid, const MatchTile* d_tiles,
+                               int n_tiles, MatchTop2* d_part, int model, const MatchGuideArgs& ga);
+// (float)(x << octave) * coord_scale, (float)(y << octave) * coord_scale of every keypoint record -> two floats per row
+void launch_match_coords(hipStream_t s, const sift_hip_keypoint* d_kp, long long rows, float coord_scale, float* d_xy);
 void launch_match_merge(hipStream_t s, const MatchTop2* d_part, const uint8_t* d_valid, const MatchBlock* d_blocks, int n_blocks,
                         int32_t* d_idx, float* d_dist);
 // records of every pair at the pair's own rows of d_seg (query order), per-pair counts; then the dense list in pair order

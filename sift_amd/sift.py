@@ -445,6 +445,109 @@ class Context:
             _raise(rc, err)
         return recs[:total.value], counts
 
+    # ---- guided matching (include/sift_hip.h, "guided matching") --------------------------------------------
+    @staticmethod
+    def _guide(model, threshold):
+        if model not in _lib.GUIDE_MODELS:
+            raise ValueError('guided matching: model must be "homography" or "fundamental"')
+        return _lib.GuideParams(_lib.GUIDE_MODELS[model], float(threshold))
+
+    @staticmethod
+    def _models9(models, n_pairs):
+        """[n, 9] float32 of a HOMOGRAPHY_DTYPE / FUNDAMENTAL_DTYPE array (as verify_images returns it) or of n x 9 numbers; a
+        tensor or an address (device memory) passes through."""
+        if isinstance(models, np.ndarray) and models.dtype.names:
+            models = models["h" if "h" in models.dtype.names else "f"]
+        if isinstance(models, (np.ndarray, list, tuple)):
+            models = np.ascontiguousarray(models, np.float32).reshape(-1, 9)
+            if models.shape[0] != n_pairs:
+                raise ValueError("guided matching: one model per pair")
+        return models
+
+    def knn2_guided_sets(self, desc, xy, offsets, pairs, models, model="homography", threshold=3.0, kp=None, idx_out=None, dist_out=None):
+        """sift_hip_knn2_guided: knn2_sets among the train rows that are admissible under the pair's model -> (idx, dist2).  `xy`:
+        two floats per row of `desc`; `models`: one per pair, a HOMOGRAPHY_DTYPE / FUNDAMENTAL_DTYPE array or [n_pairs, 9] floats;
+        xy and models may be numpy arrays, tensors or addresses (host or device memory)."""
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        pq, pt = self._pairs(pairs)
+        rows = int(sum(offsets[q + 1] - offsets[q] for q in pq if 0 <= q < offsets.size - 1))
+        idx = np.full((rows, 2), -1, np.int32) if idx_out is None else idx_out
+        dist = np.full((rows, 2), np.inf, np.float32) if dist_out is None else dist_out
+        if isinstance(desc, np.ndarray):
+            desc = np.ascontiguousarray(desc, np.float32)
+        if isinstance(xy, np.ndarray):
+            xy = np.ascontiguousarray(xy, np.float32)
+        prm = self._guide(model, threshold)
+        models = self._models9(models, pq.size)
+        err = C.create_string_buffer(512)
+        rc = self._L.sift_hip_knn2_guided(self._h, self._addr(desc), self._addr(kp), self._addr(xy), offsets.size - 1, offsets, pq.size, pq, pt,
+                                          C.byref(prm), self._addr(models), self._addr(idx), self._addr(dist), err, 512)
+        if rc:
+            _raise(rc, err)
+        return idx, dist
+
+    def knn2_guided(self, q, t, q_xy, t_xy, model_matrix, model="homography", threshold=3.0, q_kp=None, t_kp=None):
+        """Guided top-2 of the rows of `q` among `t` (numpy, host memory): `q_xy` / `t_xy` [n, 2] the rows' points, `model_matrix`
+        nine floats (query to train)."""
+        q = np.ascontiguousarray(q, np.float32).reshape(-1, 128)
+        t = np.ascontiguousarray(t, np.float32).reshape(-1, 128)
+        desc, offsets, kp = self._two_sets(q, t, q_kp, t_kp)
+        xy = np.concatenate([np.asarray(q_xy, np.float32).reshape(-1, 2), np.asarray(t_xy, np.float32).reshape(-1, 2)])
+        return self.knn2_guided_sets(desc, xy, offsets, [(0, 1)], np.asarray(model_matrix, np.float32).reshape(1, 9), model, threshold, kp)
+
+    def match_guided_sets(self, desc, xy, offsets, pairs, models, model="homography", threshold=3.0, ratio=0.8, cross_check=False, kp=None,
+                          recs_out=None):
+        """sift_hip_match_guided: match_sets under the pairs' models -> (records, counts).  Arguments as for knn2_guided_sets and
+        match_sets."""
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        pq, pt = self._pairs(pairs)
+        rows = int(sum(offsets[q + 1] - offsets[q] for q in pq if 0 <= q < offsets.size - 1))
+        recs = np.zeros(rows, _lib.MATCH_DTYPE) if recs_out is None else recs_out
+        counts = np.zeros(pq.size, np.int32)
+        total = C.c_int64()
+        if isinstance(desc, np.ndarray):
+            desc = np.ascontiguousarray(desc, np.float32)
+        if isinstance(xy, np.ndarray):
+            xy = np.ascontiguousarray(xy, np.float32)
+        mprm = _lib.MatchParams(float(ratio), 1 if cross_check else 0)
+        gprm = self._guide(model, threshold)
+        models = self._models9(models, pq.size)
+        err = C.create_string_buffer(512)
+        rc = self._L.sift_hip_match_guided(self._h, self._addr(desc), self._addr(kp), self._addr(xy), offsets.size - 1, offsets, pq.size, pq, pt,
+                                           C.byref(mprm), C.byref(gprm), self._addr(models), self._addr(recs), counts, C.byref(total), err, 512)
+        if rc:
+            _raise(rc, err)
+        return (recs[:total.value] if recs_out is None else int(total.value)), counts
+
+    def match_guided(self, q, t, q_xy, t_xy, model_matrix, model="homography", threshold=3.0, ratio=0.8, cross_check=False, q_kp=None,
+                     t_kp=None):
+        """Guided matches of the rows of `q` among `t` (numpy, host memory): records in query order."""
+        q = np.ascontiguousarray(q, np.float32).reshape(-1, 128)
+        t = np.ascontiguousarray(t, np.float32).reshape(-1, 128)
+        desc, offsets, kp = self._two_sets(q, t, q_kp, t_kp)
+        xy = np.concatenate([np.asarray(q_xy, np.float32).reshape(-1, 2), np.asarray(t_xy, np.float32).reshape(-1, 2)])
+        return self.match_guided_sets(desc, xy, offsets, [(0, 1)], np.asarray(model_matrix, np.float32).reshape(1, 9), model, threshold, ratio,
+                                      cross_check, kp)[0]
+
+    def match_images_guided(self, pairs, models, model="homography", threshold=3.0, ratio=0.8, cross_check=False):
+        """sift_hip_result_match_guided: match_images under the pairs' models, e.g. those verify_images returned, on the
+        device-resident results (the keypoints' image coordinates are built on the GPU) -> (records, counts)."""
+        pq, pt = self._pairs(pairs)
+        cnt = self.counts() if self._L.sift_hip_result_images(self._h) >= 0 else np.zeros(0, np.int32)   # none: the call says so
+        rows = int(sum(cnt[q] for q in pq if 0 <= q < cnt.size))
+        recs = np.zeros(rows, _lib.MATCH_DTYPE)
+        counts = np.zeros(pq.size, np.int32)
+        total = C.c_int64()
+        mprm = _lib.MatchParams(float(ratio), 1 if cross_check else 0)
+        gprm = self._guide(model, threshold)
+        models = self._models9(models, pq.size)
+        err = C.create_string_buffer(512)
+        rc = self._L.sift_hip_result_match_guided(self._h, pq.size, pq, pt, C.byref(mprm), C.byref(gprm), self._addr(models),
+                                                  C.c_void_p(recs.ctypes.data), counts, C.byref(total), err, 512)
+        if rc:
+            _raise(rc, err)
+        return recs[:total.value], counts
+
     # ---- geometric verification (include/sift_hip.h, "geometric verification") ----------------------------
     def ransac_homography(self, pts, offsets=None, iterations=2048, threshold=3.0, seed=0, want_scores=False, models_out=None,
                           inlier_out=None, scores_out=None, refine=0):
@@ -753,3 +856,28 @@ class Sift:
         run = self.ctx.ransac_fundamental if model == "fundamental" else self.ctx.ransac_homography
         models, inlier = run(pts, None, iterations, threshold, seed, refine=refine)
         return recs, models[0], inlier
+
+    def match_guided(self, points_a, points_b, model, threshold: float = 3.0, ratio: float = 0.8, cross_check: bool = False):
+        """match() again under the model verify() returned (an extension): a point of b competes for a point of a only when it
+        lies within `threshold` pixels of the model - of the transferred point (a homography record) or of the epipolar line (a
+        fundamental record).  Coordinates as verify() forms them.  A model that is none (all zeros) gives no records."""
+        names = getattr(getattr(model, "dtype", None), "names", None) or ()
+        if "h" not in names and "f" not in names:
+            raise ValueError("match_guided: model must be a record as verify() returns it")
+        kind = "homography" if "h" in names else "fundamental"
+        scale = np.float32(0.5 if self.subpixel else 1.0)
+
+        def rows(points):
+            d = np.zeros((len(points), 128), np.float32)
+            kp = np.zeros(len(points), _lib.KEYPOINT_DTYPE)
+            xy = np.zeros((len(points), 2), np.float32)
+            for i, p in enumerate(points):
+                xy[i] = (p.loc[0] << p.octave, p.loc[1] << p.octave)
+                if len(p.descriptors) == 128:
+                    d[i] = p.descriptors
+                    kp["has_descriptor"][i] = 1
+            return d, kp, xy * scale
+        qa, ka, xa = rows(points_a)
+        qb, kb, xb = rows(points_b)
+        return self.ctx.match_guided(qa, qb, xa, xb, np.asarray(model["h" if kind == "homography" else "f"], np.float32), kind, threshold,
+                                     ratio, cross_check, ka, kb)

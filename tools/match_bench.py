@@ -12,6 +12,13 @@ events as well.  Achieved TF/s = 2 * nq * nt * 128 / time, beside the 157.3 TF f
 an untuned f32 MFMA GEMM.  On (a), 256 sampled query rows are compared bit for bit with the host checker.
 
     python tools/match_bench.py [--reps 20] [--frames 32] [--out profiles/match_bench.txt]
+
+--guided-arm: guided matching instead (no torch arm).  On cases (a) and (b), without and with the cross-check, and for both
+models, sift_hip_result_match alternates with sift_hip_result_match_guided under (1) the models of a preceding verify_images at
+3 px, (2) a model and a threshold that admit every row (the early skip of the tile kernel works as in the unguided kernel) and
+(3) a band of 3 px under a fixed model (nearly every candidate is inadmissible, a lane's second best stays +inf for long).  The
+frames of the bench batch are unrelated, so (1) is a narrow band too.  Median, min and max of --reps; lines are appended to
+--out.  --unguided-only: the unguided calls of those cases alone (for an A/B of two builds, SIFT_HIP_LIBRARY).
 """
 import argparse
 import json
@@ -37,6 +44,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--guided-arm", action="store_true")
+    ap.add_argument("--unguided-only", action="store_true")
     args = ap.parse_args()
 
     import torch
@@ -81,11 +90,56 @@ def main():
                 "torch_tflops": round(flop / (t["median_ms"] * 1e-3) / 1e12, 2), "speedup_vs_torch": round(t["median_ms"] / f["median_ms"], 2),
                 "f32_matrix_peak_tflops": 157.3, "untuned_mfma_gemm_tflops": 122}
 
+    def timed(arms):
+        """Alternate the arms (name -> call); host time around each call."""
+        for _ in range(args.warmup):
+            for fn in arms.values():
+                fn()
+        ms = {k: [] for k in arms}
+        for _ in range(args.reps):
+            for k, fn in arms.items():
+                t0 = time.perf_counter()
+                fn()
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+        return {k: stats(v) for k, v in ms.items()}
+
+    def guided_arms(ctx, cnt):
+        identity = np.array([1, 0, 0, 0, 1, 0, 0, 0, 1], np.float32)
+        f_all = np.array([0, 0, 1, 0, 0, 0, 0, 0, 0], np.float32)            # a = 1, b = 0: g > 0 at every row
+        f_rows = np.array([0, 0, 0, 0, 0, -1, 0, 1, 0], np.float32)          # epipolar lines ty = qy
+        n = cnt.size
+        for name, pairs in (("a: frames 1 and 2", [(0, 1)]), (f"b: the {n - 1} consecutive pairs", [(i, i + 1) for i in range(n - 1)])):
+            for cross in (False, True):
+                arms = {"unguided": lambda: ctx.match_images(pairs, 0.8, cross)}
+                if args.unguided_only:
+                    emit({"case": name, "cross_check": cross, "library": os.path.basename(_lib.LIB_PATH), **timed(arms)})
+                    continue
+                found = {}
+                for kind, every, fixed in (("homography", identity, identity), ("fundamental", f_all, f_rows)):
+                    models = ctx.verify_images(pairs, 0.8, cross, 512, 3.0, 0, model=kind)[2]
+                    tile = lambda m: np.tile(m, (len(pairs), 1))   # noqa: E731
+                    arms[kind + " verified 3 px"] = lambda m=models, k=kind: ctx.match_images_guided(pairs, m, k, 3.0, 0.8, cross)
+                    arms[kind + " admit-all"] = lambda m=tile(every), k=kind: ctx.match_images_guided(pairs, m, k, 1e30, 0.8, cross)
+                    arms[kind + " fixed model 3 px"] = lambda m=tile(fixed), k=kind: ctx.match_images_guided(pairs, m, k, 3.0, 0.8, cross)
+                    found[kind] = int((models["iteration"] >= 0).sum())
+                res = timed(arms)
+                emit({"case": "guided, " + name, "cross_check": cross, "pairs_with_a_verified_model": found,
+                      "matches": {k: int(fn()[0].size) for k, fn in arms.items()}, **res})
+
     ctx = Context(0)
     # ---- (a) and (b): the bench batch ----
     n = args.frames
     ctx.calculate_batch(synth_batch(n, 1920, 1080), _lib.Params(3, 4, 1.6, K_SQRT2, 0))
     cnt = ctx.counts()
+    if args.guided_arm or args.unguided_only:
+        guided_arms(ctx, cnt)
+        ctx.close()
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write("# tools/match_bench.py --guided-arm: sift_hip_result_match alternating with sift_hip_result_match_guided (ms on the host around each call)\n"
+                        if args.guided_arm else "# tools/match_bench.py --unguided-only\n")
+                f.write("\n".join(lines) + "\n")
+        return
     off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
     kp, desc = ctx.results()
     d_kp, d_desc = ctx.result_device_ptrs()
