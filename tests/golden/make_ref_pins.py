@@ -3,6 +3,7 @@
 
     python tests/golden/make_ref_pins.py                                   (in the build container, where /root/reference is mounted)
     python tests/golden/make_ref_pins.py bench_frame | config2 | truncation | configs | config5   (the long-running pins, one fixture each)
+    python tests/golden/make_ref_pins.py hard_frames                       (HARD_CASES -> refpin_hard_frames.npz; refpin.npz is not rewritten)
 
 /root/reference/bin/arch_x64/sift cannot be started here (Vigra, OpenCV, Boost are DT_NEEDED and absent) and the
 sources cannot be rebuilt for the same reason, but `Sift::calculate` and the `sift::alg` functions inside it only need
@@ -34,7 +35,7 @@ K_SQRT2 = float(np.float32(np.sqrt(np.float32(2.0))))
 POINT_DTYPE = np.dtype([("x", "<u2"), ("y", "<u2"), ("octave", "<u2"), ("index", "<u2"), ("filtered", "<u2"), ("pad", "<u2"),
                         ("scale", "<f4"), ("orientation", "<f4"), ("n_desc", "<u4")])
 
-# name -> (image spec, dogs, octaves, subpixel).  image spec: ("synth", w, h, seed) | ("parrot",) | ("const", w, h, value)
+# name -> (image spec, dogs, octaves, subpixel).  image spec: ("synth", w, h, seed) | ("parrot",) | ("const", w, h, value) | ("hard", kind, w, h)
 CALC_CASES = {
     "synth_200x160_3x2": (("synth", 200, 160, 2), 3, 2, 0),
     "synth_320x250_3x3": (("synth", 320, 250, 4), 3, 3, 0),
@@ -50,6 +51,16 @@ CALC_CASES = {
     "synth_1000x760_3x3": (("synth", 1000, 760, 21), 3, 3, 0),     # 122 k candidates, 7.4 k survivors: the unstable sort's order at scale
     # (App. B-7, more than 65535 SURVIVORS, needs ~8 Mpx: hours in the reference's O(K x N) descriptor stage - not pinned)
 }
+# Content of other kinds (tests/hard_frames.py), a table and a fixture of their own (refpin_hard_frames.npz, same keys): zero-mean
+# pixels - several orientation peaks per keypoint, the keypoint duplicated per peak with the first peak twice (sift.cpp:190-199,
+# App. B-18) -, a two-valued frame - NaN orientations, all-zero descriptors (B-9, B-11) -, saturated plateaus, exact mirror symmetry
+HARD_CASES = {
+    "signed_160x120_3x2": (("hard", "signed", 160, 120), 3, 2, 0),
+    "binary_160x120_3x2": (("hard", "binary", 160, 120), 3, 2, 0),
+    "saturated_160x120_3x2": (("hard", "saturated", 160, 120), 3, 2, 0),
+    "mirror4_160x120_3x2": (("hard", "mirror4", 160, 120), 3, 2, 0),
+}
+HARD_PIN = os.path.join(HERE, "refpin_hard_frames.npz")
 BLUR_SIGMAS = [0.3, 1.0, 1.6, 2.0, 2.2627418, 3.2, 4.5254836, 6.4]
 BLUR_IMAGES = [("synth", 200, 150, 3), ("synth", 67, 131, 4), ("synth", 64, 64, 5)]
 PARABOLAS = [(3, 1.5, 4, 2.5, 5, 1.0), (0, 0.25, 1, 0.75, 2, 0.5), (34, 12.0, 35, 12.0, 0, 3.0), (10, 1.0, 11, 1.0, 12, 1.0)]
@@ -60,6 +71,9 @@ def make_image(spec):
         return synth_frame(spec[1], spec[2], spec[3])
     if spec[0] == "const":
         return np.full((spec[2], spec[1]), spec[3], np.float32)
+    if spec[0] == "hard":
+        from hard_frames import hard_frame
+        return hard_frame(spec[1], spec[2], spec[3])
     return read_pgm(os.path.join(HERE, "parrot_r.pgm"))
 
 
@@ -115,37 +129,43 @@ def ref_calculate(img, dogs, octaves, subpixel, tmp):
     return res
 
 
+def store_calc(store, name, case, tmp):
+    """One case of a calculate table: what the reference returned for it, into `store` under calc/<name>/."""
+    spec, dogs, octaves, sub = case
+    img = make_image(spec)
+    r = ref_calculate(img, dogs, octaves, sub, tmp)
+    store[f"calc/{name}/params"] = np.array([dogs, octaves, sub, img.shape[1], img.shape[0]], np.int64)
+    store[f"calc/{name}/image_sha"] = np.array(sha(img))
+    if "exception" in r:
+        store[f"calc/{name}/exception"] = np.array(r["exception"])
+        print(f"{name}: EXCEPTION {r['exception']!r}")
+        return
+    store[f"calc/{name}/points"] = r["points"]
+    store[f"calc/{name}/desc_sha"] = np.array(hashlib.sha256(r["desc"].tobytes()).hexdigest())
+    store[f"calc/{name}/levels_wh"] = np.array(r["levels_wh"], np.int64)
+    store[f"calc/{name}/level_dims"] = r["level_dims"]
+    store[f"calc/{name}/level_scale_bits"] = r["level_scale_bits"]
+    store[f"calc/{name}/level_sha"] = np.array(r["level_sha"])
+    store[f"calc/{name}/image_dims"] = r["image_dims"]
+    store[f"calc/{name}/mag_sha"] = np.array(r["mag_sha"])
+    store[f"calc/{name}/ori_sha"] = np.array(r["ori_sha"])
+    store[f"calc/{name}/dogs_wh"] = np.array(r["dogs_wh"], np.int64)
+    store[f"calc/{name}/dog_dims"] = r["dog_dims"]
+    store[f"calc/{name}/dog_scale_bits"] = r["dog_scale_bits"]
+    store[f"calc/{name}/dog_sha"] = np.array(r["dog_sha"])
+    if name == "synth_200x160_3x2":      # one small case in full
+        store[f"calc/{name}/desc"] = r["desc"]
+        store[f"calc/{name}/levels"] = r["levels"]
+    print(f"{name}: {r['points'].size} points, {int((r['points']['n_desc'] == 128).sum())} with descriptors")
+
+
 def main():
     assert os.path.exists(REF_BIN), "the reference is not mounted here"
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "_ref/refexec"])
     store = {}
     with tempfile.TemporaryDirectory() as tmp:
-        for name, (spec, dogs, octaves, sub) in CALC_CASES.items():
-            img = make_image(spec)
-            r = ref_calculate(img, dogs, octaves, sub, tmp)
-            store[f"calc/{name}/params"] = np.array([dogs, octaves, sub, img.shape[1], img.shape[0]], np.int64)
-            store[f"calc/{name}/image_sha"] = np.array(sha(img))
-            if "exception" in r:
-                store[f"calc/{name}/exception"] = np.array(r["exception"])
-                print(f"{name}: EXCEPTION {r['exception']!r}")
-                continue
-            store[f"calc/{name}/points"] = r["points"]
-            store[f"calc/{name}/desc_sha"] = np.array(hashlib.sha256(r["desc"].tobytes()).hexdigest())
-            store[f"calc/{name}/levels_wh"] = np.array(r["levels_wh"], np.int64)
-            store[f"calc/{name}/level_dims"] = r["level_dims"]
-            store[f"calc/{name}/level_scale_bits"] = r["level_scale_bits"]
-            store[f"calc/{name}/level_sha"] = np.array(r["level_sha"])
-            store[f"calc/{name}/image_dims"] = r["image_dims"]
-            store[f"calc/{name}/mag_sha"] = np.array(r["mag_sha"])
-            store[f"calc/{name}/ori_sha"] = np.array(r["ori_sha"])
-            store[f"calc/{name}/dogs_wh"] = np.array(r["dogs_wh"], np.int64)
-            store[f"calc/{name}/dog_dims"] = r["dog_dims"]
-            store[f"calc/{name}/dog_scale_bits"] = r["dog_scale_bits"]
-            store[f"calc/{name}/dog_sha"] = np.array(r["dog_sha"])
-            if name == "synth_200x160_3x2":      # one small case in full
-                store[f"calc/{name}/desc"] = r["desc"]
-                store[f"calc/{name}/levels"] = r["levels"]
-            print(f"{name}: {r['points'].size} points, {int((r['points']['n_desc'] == 128).sum())} with descriptors")
+        for name, case in CALC_CASES.items():
+            store_calc(store, name, case, tmp)
         for spec in BLUR_IMAGES:
             img = make_image(spec)
             h, w = img.shape
@@ -180,6 +200,17 @@ def main():
     dst = os.path.join(HERE, os.environ.get("REFPIN_OUT", "refpin.npz"))
     np.savez_compressed(dst, **store)
     print("wrote", dst, os.path.getsize(dst), "bytes")
+
+
+def hard_frames():
+    assert os.path.exists(REF_BIN), "the reference is not mounted here"
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "_ref/refexec"])
+    store = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for name, case in HARD_CASES.items():
+            store_calc(store, name, case, tmp)
+    np.savez_compressed(HARD_PIN, **store)
+    print("wrote", HARD_PIN, os.path.getsize(HARD_PIN), "bytes")
 
 
 def long_running(which):
@@ -256,7 +287,9 @@ def long_running(which):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1:
+    if sys.argv[1:] == ["hard_frames"]:
+        hard_frames()
+    elif len(sys.argv) > 1:
         long_running(sys.argv[1])
     else:
         main()

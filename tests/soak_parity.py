@@ -4,7 +4,9 @@ level, stage list, orientation and descriptor against the CPU oracle bit for bit
 Not collected by `pytest tests/` (the file name does not match): a run takes as long as it is given.  The fixed cases of
 the suite were chosen for the kernels' known boundaries; this draws the rest of the space - widths of every residue
 modulo 2 / 4 / 64 / 128, strips that end inside the image, chunks of odd row counts, levels close to the smallest the
-reference accepts, batches of 1 - 3.
+reference accepts, batches of 1 - 3 - and, beside the value noise and the blob lattice, the frames of tests/hard_frames.py (negative
+pixels: several orientation peaks and the whole batch redone on the host; two-valued: NaN orientations; plateaus, mirror symmetry,
+periodic patterns, impulses, other value ranges).
     python3 tests/soak_parity.py [seconds=600] [seed=1] [big]
 ("big": shapes 1000..4096 x 700..2200, batches of 1 - 6 - launches large enough to take the streaming kernels by themselves.)
 Prints one line per case and a summary; exits 1 if any case differed.
@@ -24,6 +26,7 @@ for p_ in (os.path.join(HERE, "golden"), HERE, os.path.dirname(HERE)):   # what 
 from sift_amd import _lib                                  # noqa: E402
 from sift_amd.sift import Context                          # noqa: E402
 from sift_amd.synthetic import blob_frame, synth_frame     # noqa: E402
+from hard_frames import GENERATORS                         # noqa: E402
 from test_gpu_parity import compare_run                    # noqa: E402
 
 
@@ -34,7 +37,7 @@ def draw_big(rng):
         w = w // 4 * 4
     frames = int(rng.choice([1, 2, 3, 4, 6])) if w * h < 3000 * 1000 else int(rng.choice([1, 2]))
     return dict(w=w, h=h, dogs=int(rng.choice([3, 3, 4])), octaves=int(rng.integers(2, 6)), sigma=float(rng.choice([1.6, 1.6, 1.2])), subpixel=False,
-                frames=frames, streaming=0, blobs=False, seed=int(rng.integers(1, 1 << 20)))
+                frames=frames, streaming=0, blobs=False, seed=int(rng.integers(1, 1 << 20)), hard="")
 
 
 def draw(rng):
@@ -55,7 +58,12 @@ def draw(rng):
     streaming = int(rng.random() < 0.5)
     blobs = rng.random() < 0.1 and w * h <= 200 * 1000
     seed = int(rng.integers(1, 1 << 20))
-    return dict(w=w, h=h, dogs=dogs, octaves=octaves, sigma=sigma, subpixel=subpixel, frames=frames, streaming=streaming, blobs=blobs, seed=seed)
+    hard = ""
+    if not blobs and rng.random() < 0.25:      # a third content kind; drawn last, so the cases of earlier soaks keep their numbers up to here
+        hard = str(rng.choice(sorted(GENERATORS)))
+        if hard == "mirror4":
+            w, h = w // 2 * 2, h // 2 * 2
+    return dict(w=w, h=h, dogs=dogs, octaves=octaves, sigma=sigma, subpixel=subpixel, frames=frames, streaming=streaming, blobs=blobs, seed=seed, hard=hard)
 
 
 def main():
@@ -68,8 +76,11 @@ def main():
     done, failed, skipped = 0, [], 0
     while time.time() < t_end:
         c = draw_big(rng) if big else draw(rng)
-        name = "soak %(w)dx%(h)d dogs %(dogs)d oct %(octaves)d sigma %(sigma)g sub %(subpixel)d x%(frames)d stream %(streaming)d blobs %(blobs)d seed %(seed)d" % c
-        img = blob_frame(c["w"], c["h"], 3 + c["seed"] % 5) if c["blobs"] else synth_frame(c["w"], c["h"], c["seed"])
+        name = "soak %(w)dx%(h)d dogs %(dogs)d oct %(octaves)d sigma %(sigma)g sub %(subpixel)d x%(frames)d stream %(streaming)d blobs %(blobs)d seed %(seed)d %(hard)s" % c
+        if c["hard"]:
+            img = GENERATORS[c["hard"]](c["w"], c["h"], c["seed"])
+        else:
+            img = blob_frame(c["w"], c["h"], 3 + c["seed"] % 5) if c["blobs"] else synth_frame(c["w"], c["h"], c["seed"])
         ctx.set_option("stream_min_waves", 1 if c["streaming"] else 0)
         t0 = time.time()
         try:

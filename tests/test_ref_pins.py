@@ -28,20 +28,25 @@ def vigra_text(msg: str) -> str:
 
 
 CALC = sorted(G.CALC_CASES)
+HARD = sorted(G.HARD_CASES)       # tests/hard_frames.py's content, pinned in a fixture of its own
+HARD_PIN = np.load(G.HARD_PIN)
+ALL_CASES = {**G.CALC_CASES, **G.HARD_CASES}
+assert len(ALL_CASES) == len(CALC) + len(HARD)
 
 
-@pytest.mark.parametrize("name", CALC)
+@pytest.mark.parametrize("name", CALC + HARD)
 def test_calculate_matches_the_reference_binary(name):
-    spec, dogs, octaves, sub = G.CALC_CASES[name]
+    pin = HARD_PIN if name in G.HARD_CASES else PIN
+    spec, dogs, octaves, sub = ALL_CASES[name]
     img = G.make_image(spec)
-    assert sha(img) == str(PIN[f"calc/{name}/image_sha"]), "input differs from the one the reference saw"
+    assert sha(img) == str(pin[f"calc/{name}/image_sha"]), "input differs from the one the reference saw"
     run = O.OracleRun(img, dogs, octaves, subpixel=bool(sub))
-    if f"calc/{name}/exception" in PIN.files:
+    if f"calc/{name}/exception" in pin.files:
         assert run.status == 1
-        assert vigra_text(run.error).strip() == vigra_text(str(PIN[f"calc/{name}/exception"])).strip()
+        assert vigra_text(run.error).strip() == vigra_text(str(pin[f"calc/{name}/exception"])).strip()
         return
     assert run.status == 0, run.error
-    ref = PIN[f"calc/{name}/points"]
+    ref = pin[f"calc/{name}/points"]
     got, gdesc = run.points("final")
     assert got.size == ref.size
     for f in ("x", "y", "octave", "index"):
@@ -51,30 +56,30 @@ def test_calculate_matches_the_reference_binary(name):
     assert got["orientation"].tobytes() == ref["orientation"].tobytes()
     assert (got["n_desc"] == ref["n_desc"]).all()
     d = np.concatenate([gdesc[i, :got["n_desc"][i]] for i in range(got.size)]) if got.size else np.zeros(0, np.float32)
-    assert hashlib.sha256(d.astype(np.float32).tobytes()).hexdigest() == str(PIN[f"calc/{name}/desc_sha"])
+    assert hashlib.sha256(d.astype(np.float32).tobytes()).hexdigest() == str(pin[f"calc/{name}/desc_sha"])
     # the Gaussian pyramid the reference object kept: Matrix<OctaveElem>(octaves, dogs + 1), element (o, j)
-    mw, mh = (int(v) for v in PIN[f"calc/{name}/levels_wh"])
+    mw, mh = (int(v) for v in pin[f"calc/{name}/levels_wh"])
     assert (mw, mh) == (octaves, dogs + 1)
     for o in range(mw):
         for j in range(mh):
             lv = run.level("gaussian", o, j)
             k = o * mh + j
-            assert tuple(PIN[f"calc/{name}/level_dims"][k]) == (lv.shape[1], lv.shape[0])
-            assert np.float32(run.scale("gaussian", o, j)).view(np.uint32) == PIN[f"calc/{name}/level_scale_bits"][k]
-            assert sha(lv) == str(PIN[f"calc/{name}/level_sha"][k]), f"gaussian({o},{j})"
-    w, h = (int(v) for v in PIN[f"calc/{name}/image_dims"])
+            assert tuple(pin[f"calc/{name}/level_dims"][k]) == (lv.shape[1], lv.shape[0])
+            assert np.float32(run.scale("gaussian", o, j)).view(np.uint32) == pin[f"calc/{name}/level_scale_bits"][k]
+            assert sha(lv) == str(pin[f"calc/{name}/level_sha"][k]), f"gaussian({o},{j})"
+    w, h = (int(v) for v in pin[f"calc/{name}/image_dims"])
     assert run.image().shape == (h, w)          # subpixel: the caller's image was replaced (sift.cpp:20-21)
     # the DoG pyramid (Sift::_createDOGs called on its own): Matrix<OctaveElem>(octaves, dogs)
     # (with subpixel, calculate() upsamples before it calls _createDOGs, sift.cpp:20-22: the stand-alone call saw the raw frame)
-    dw, dh = (int(v) for v in PIN[f"calc/{name}/dogs_wh"])
+    dw, dh = (int(v) for v in pin[f"calc/{name}/dogs_wh"])
     assert (dw, dh) == (octaves, dogs)
     for o in range(dw if not sub else 0):
         for j in range(dh):
             lv = run.level("dog", o, j)
             k = o * dh + j
-            assert tuple(PIN[f"calc/{name}/dog_dims"][k]) == (lv.shape[1], lv.shape[0])
-            assert np.float32(run.scale("dog", o, j)).view(np.uint32) == PIN[f"calc/{name}/dog_scale_bits"][k]
-            assert sha(lv) == str(PIN[f"calc/{name}/dog_sha"][k]), f"dog({o},{j})"
+            assert tuple(pin[f"calc/{name}/dog_dims"][k]) == (lv.shape[1], lv.shape[0])
+            assert np.float32(run.scale("dog", o, j)).view(np.uint32) == pin[f"calc/{name}/dog_scale_bits"][k]
+            assert sha(lv) == str(pin[f"calc/{name}/dog_sha"][k]), f"dog({o},{j})"
     # the gradient maps in their FINAL state: the descriptor stage has added to them in place, keypoint after keypoint.
     # The reference keeps maps of every Gaussian level, the oracle of the levels some keypoint selects.
     checked = 0
@@ -83,13 +88,13 @@ def test_calculate_matches_the_reference_binary(name):
             for kind, key in (("magnitude", "mag_sha"), ("orientation", "ori_sha")):
                 lv = run.level(kind, o, j)
                 if lv is not None:
-                    assert sha(lv) == str(PIN[f"calc/{name}/{key}"][o * mh + j]), f"{kind}({o},{j})"
+                    assert sha(lv) == str(pin[f"calc/{name}/{key}"][o * mh + j]), f"{kind}({o},{j})"
                     checked += 1
     assert checked >= 2 or ref.size == 0
-    if f"calc/{name}/desc" in PIN.files:        # the small case stored in full
-        assert d.tobytes() == PIN[f"calc/{name}/desc"].tobytes()
+    if f"calc/{name}/desc" in pin.files:        # the small case stored in full
+        assert d.tobytes() == pin[f"calc/{name}/desc"].tobytes()
         flat = np.concatenate([run.level("gaussian", o, j).reshape(-1) for o in range(mw) for j in range(mh)])
-        assert flat.tobytes() == PIN[f"calc/{name}/levels"].tobytes()
+        assert flat.tobytes() == pin[f"calc/{name}/levels"].tobytes()
 
 
 @pytest.mark.parametrize("spec", G.BLUR_IMAGES, ids=[f"{s[1]}x{s[2]}" for s in G.BLUR_IMAGES])
@@ -135,6 +140,29 @@ def test_fixture_is_what_the_reference_binary_returns_now(tmp_path):
     assert r["points"].tobytes() == PIN[f"calc/{name}/points"].tobytes()
     assert r["desc"].tobytes() == PIN[f"calc/{name}/desc"].tobytes()
     assert r["levels"].tobytes() == PIN[f"calc/{name}/levels"].tobytes()
+
+
+@pytest.mark.skipif(not os.path.exists(G.REF_BIN), reason="the reference is only mounted in the build container")
+@pytest.mark.parametrize("name", HARD)
+def test_hard_frame_fixture_is_what_the_reference_binary_returns_now(name, tmp_path):
+    """Live, for the frames of tests/hard_frames.py: what the binary returns now against the fixture, and - the fixture keeps
+    descriptors and levels as hashes only - against the oracle in full: every point record (several records per keypoint with
+    the first peak twice for `signed`, NaN orientations for `binary`), every descriptor float and every Gaussian level."""
+    root = os.path.dirname(HERE)
+    subprocess.check_call(["make", "-s", "-C", os.path.join(root, "oracle"), "_ref/refexec"])
+    spec, dogs, octaves, sub = G.HARD_CASES[name]
+    img = G.make_image(spec)
+    r = G.ref_calculate(img, dogs, octaves, sub, str(tmp_path))
+    assert r["points"].tobytes() == HARD_PIN[f"calc/{name}/points"].tobytes()
+    assert hashlib.sha256(r["desc"].tobytes()).hexdigest() == str(HARD_PIN[f"calc/{name}/desc_sha"])
+    assert list(r["level_sha"]) == [str(v) for v in HARD_PIN[f"calc/{name}/level_sha"]]
+    run = O.OracleRun(img, dogs, octaves, subpixel=bool(sub))
+    got, gdesc = run.points("final")
+    d = _compare_points(got, gdesc, r["points"])
+    assert d.tobytes() == r["desc"].tobytes()
+    mw, mh = r["levels_wh"]
+    flat = np.concatenate([run.level("gaussian", o, j).reshape(-1) for o in range(mw) for j in range(mh)])
+    assert flat.tobytes() == r["levels"].tobytes()
 
 
 # ---- two long-running pins (tens of minutes to hours in the reference: it copies three DoG images per candidate and
