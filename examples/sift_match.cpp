@@ -1,7 +1,8 @@
 // Two images -> matches.txt: sift::Sift::calculate() on both, sift::Matcher::match() on their points (include/sift/match.hpp; an
 // extension, the reference has no matcher).  One line per match: `query train dist2 second2`, positions in the two point lists.
 //   g++ -std=c++17 -pthread -Iinclude examples/sift_match.cpp -Lsift_amd/lib -lsift_hip -Wl,-rpath,$PWD/sift_amd/lib -o sift_match
-//   ./sift_match a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0]
+//   ./sift_match a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [quantized=0]
+// quantized=1: 8-bit descriptors, integer distances (the distances in matches.txt are then integers).
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -24,19 +25,20 @@ static std::vector<sift::InterestPoint> points_of(sift::Sift& sift, const std::s
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        std::cerr << "usage: " << argv[0] << " a.{pgm,ppm,png,jpg} b.{...} [octaves] [dogsPerEpoch] [ratio] [crossCheck]\n";
+        std::cerr << "usage: " << argv[0] << " a.{pgm,ppm,png,jpg} b.{...} [octaves] [dogsPerEpoch] [ratio] [crossCheck] [quantized]\n";
         return 1;
     }
     const u16_t octaves = argc > 3 ? (u16_t)std::atoi(argv[3]) : 4;
     const u16_t dogsPerEpoch = argc > 4 ? (u16_t)std::atoi(argv[4]) : 3;
     const float ratio = argc > 5 ? (float)std::atof(argv[5]) : 0.8f;
     const bool crossCheck = argc > 6 && std::atoi(argv[6]) != 0;
+    const bool quantized = argc > 7 && std::atoi(argv[7]) != 0;
     try {
         sift::Sift sift(dogsPerEpoch, octaves, 1.6f, std::sqrt(2.0f), false);
         const std::vector<sift::InterestPoint> a = points_of(sift, argv[1]);
         const std::vector<sift::InterestPoint> b = points_of(sift, argv[2]);
         sift::Matcher matcher;
-        const std::vector<sift::Match> matches = matcher.match(a, b, ratio, crossCheck);
+        const std::vector<sift::Match> matches = matcher.match(a, b, ratio, crossCheck, quantized);
         FILE* out = std::fopen("matches.txt", "w");
         if (!out) throw std::runtime_error("cannot write matches.txt");
         for (const sift::Match& m : matches) std::fprintf(out, "%d %d %.9g %.9g\n", m.query, m.train, (double)m.dist2, (double)m.second2);

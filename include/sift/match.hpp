@@ -49,9 +49,11 @@ public:
 
     // Matches of `query` among `train`, in the order of `query`.  ratio 0: no ratio test, else 0 < ratio <= 1 (Lowe's test on
     // squared distances: dist2 < ratio^2 * second2); crossCheck: keep a match only if it is also the best one seen from the
-    // train point.  A point without a 128-float descriptor takes no part.
+    // train point.  A point without a 128-float descriptor takes no part.  quantized: the descriptors are quantised to 8 bits on
+    // the GPU and matched by the integer distance on the i8 matrix cores (include/sift_hip.h, "8-bit descriptors and integer
+    // matching"); dist2 and second2 are then integers, sum (a - b)^2 over the 128 bytes.
     std::vector<Match> match(const std::vector<InterestPoint>& query, const std::vector<InterestPoint>& train, f32_t ratio = 0.8f,
-                             bool crossCheck = false) {
+                             bool crossCheck = false, bool quantized = false) {
         const size_t nq = query.size(), nt = train.size();
         rows(query, train);
         const int64_t offsets[3] = {0, (int64_t)nq, (int64_t)(nq + nt)};
@@ -59,6 +61,7 @@ public:
         sift_hip_match_params prm{};
         prm.ratio = ratio;
         prm.cross_check = crossCheck ? 1 : 0;
+        prm.quantized = quantized ? 1 : 0;
         _recs.resize(nq);
         int32_t count = 0;
         int64_t total = 0;

@@ -215,8 +215,11 @@ int sift_hip_image_copy(sift_hip_ctx* ctx, int image, float* out);
 typedef struct sift_hip_match_params {
     float ratio;          /* 0: no ratio test; else 0 < ratio <= 1: keep when d2_best < (ratio * ratio) * d2_second */
     uint8_t cross_check;  /* keep a row only if it is the best query row of its best train row (same order, same query set) */
-    uint8_t reserved[3];
-} sift_hip_match_params;
+    uint8_t quantized;    /* 0: float rows, the definition above.  1: the rows are quantised to 8 bits on the device and matched by
+                           * the integer distance ("8-bit descriptors and integer matching" below).  Above 1: SIFT_HIP_EINVAL.  This
+                           * byte used to be reserved: it must be zero for the behaviour before it had a meaning. */
+    uint8_t reserved[2];
+} sift_hip_match_params;  /* 8 bytes */
 typedef struct sift_hip_match_rec {
     int32_t query, train; /* rows of the pair's query / train set */
     float dist2, second2; /* d2 of the best and of the second best (+inf: none) */
@@ -403,6 +406,40 @@ int sift_hip_match_guided(sift_hip_ctx* ctx, const float* desc, const sift_hip_k
 int sift_hip_result_match_guided(sift_hip_ctx* ctx, int n_pairs, const int32_t* pair_q, const int32_t* pair_t,
                                  const sift_hip_match_params* match_params, const sift_hip_guide_params* guide, const float* models,
                                  sift_hip_match_rec* recs, int32_t* counts, int64_t* total, char* err, int errlen);
+
+/* ---- 8-bit descriptors and integer matching (an extension) --------------------------------------------------
+ * A descriptor row as 128 bytes - the format SIFT files and structure-from-motion tools keep, a quarter of the float row - and
+ * descriptor matching over such rows on the i8 matrix instruction of gfx950.  Every element of a descriptor of this library
+ * lies in [0, 1] (each 4 x 4 cell is L1-normalised on its own), so the scale is linear and needs no clipping constant.
+ *   Quantiser  for a float v: t = fmaf(v, 255.0f, 0.5f); q(v) = 255 when t >= 255.0f, (uint8_t)(int)t when t >= 0.0f (the cast
+ *              truncates), 0 otherwise.  A NaN, -inf and negative values give 0, +inf gives 255; no libm call, no dependence
+ *              on a rounding mode.
+ *   Distance   d2(a, b) = sum over the 128 bytes of (a[k] - b[k])^2: an exact integer, at most 128 * 255^2 = 8 323 200 < 2^24,
+ *              the same number in every summation order.  Wherever a distance leaves the library (dist2[], the records' dist2 /
+ *              second2) it is (float)d2, which is exact.  A missing entry is index -1, distance +inf, as for float rows.
+ *   The rest   is "descriptor matching" above, unchanged: validity from kp[].has_descriptor (no kp: every row valid), candidates
+ *              ordered by (d2, j) - the lowest index wins a tie, and ties are common now -, the ratio test dist2 < (ratio *
+ *              ratio) * second2 in float, the cross-check, sets, pairs, offsets, the memory rules, one launch of each kernel per
+ *              call, independence from tiles and splits.  There is no NaN case.
+ * A plain int32 host loop (hostmath_match_knn2_u8, with hostmath_quantize) checks every bit.  Byte rows, and float rows that
+ * are to be quantised, must be aligned to 16 bytes when they lie in device memory (SIFT_HIP_EINVAL otherwise).
+ *
+ * sift_hip_match_params.quantized = 1 in sift_hip_match, sift_hip_result_match, sift_hip_result_verify and
+ * sift_hip_result_verify_fundamental: the float rows are quantised on the device into scratch memory kept with the context and
+ * the integer matcher runs - bit for bit sift_hip_quantize followed by sift_hip_match_u8.  In the three guided calls
+ * quantized = 1 is SIFT_HIP_EINVAL: guided matching takes float rows only.  The two _u8 calls below take bytes whatever the
+ * flag says (0 or 1). */
+/* rows x 128 floats -> rows x 128 bytes; each side may be host or device memory; zero rows is legal. */
+int sift_hip_quantize(sift_hip_ctx* ctx, const float* desc, int64_t rows, uint8_t* out, char* err, int errlen);
+/* The descriptors of the last batch, quantised on the GPU: sift_hip_result_total() * 128 bytes to host or device memory,
+ * bit for bit the quantiser over what sift_hip_result_copy delivers.  SIFT_HIP_EINVAL when the context holds no results. */
+int sift_hip_result_copy_u8(sift_hip_ctx* ctx, uint8_t* descriptors);
+/* sift_hip_knn2 and sift_hip_match over byte rows, for callers who keep bytes. */
+int sift_hip_knn2_u8(sift_hip_ctx* ctx, const uint8_t* desc, const sift_hip_keypoint* kp, int n_sets, const int64_t* offsets,
+                     int n_pairs, const int32_t* pair_q, const int32_t* pair_t, int32_t* idx, float* dist2, char* err, int errlen);
+int sift_hip_match_u8(sift_hip_ctx* ctx, const uint8_t* desc, const sift_hip_keypoint* kp, int n_sets, const int64_t* offsets,
+                      int n_pairs, const int32_t* pair_q, const int32_t* pair_t, const sift_hip_match_params* params,
+                      sift_hip_match_rec* recs, int32_t* counts, int64_t* total, char* err, int errlen);
 
 /* ---- inspection of the last batch (parity tests) ------------------------------------------------ */
 /* kind: 0 gaussian (levels 0..D), 1 dog (0..D-1), 2 magnitude, 3 orientation (initial gradient

@@ -39,6 +39,7 @@ SYMBOLS = [
     "sift_hip_ransac_homography", "sift_hip_result_verify", "sift_hip_refine_homography",
     "sift_hip_ransac_fundamental", "sift_hip_result_verify_fundamental",
     "sift_hip_knn2_guided", "sift_hip_match_guided", "sift_hip_result_match_guided",
+    "sift_hip_quantize", "sift_hip_result_copy_u8", "sift_hip_knn2_u8", "sift_hip_match_u8",
 ]
 
 
@@ -48,7 +49,7 @@ class Params(C.Structure):
 
 
 class MatchParams(C.Structure):
-    _fields_ = [("ratio", C.c_float), ("cross_check", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+    _fields_ = [("ratio", C.c_float), ("cross_check", C.c_uint8), ("quantized", C.c_uint8), ("reserved", C.c_uint8 * 2)]
 
 
 class GuideParams(C.Structure):
@@ -214,5 +215,10 @@ def load():
     L.sift_hip_match_guided.argtypes = [vp, vp, vp, vp, ci, i64p, ci, i32p, i32p, C.POINTER(MatchParams), gp, vp, vp, i32p,
                                         C.POINTER(C.c_int64), cs, ci]
     L.sift_hip_result_match_guided.argtypes = [vp, ci, i32p, i32p, C.POINTER(MatchParams), gp, vp, vp, i32p, C.POINTER(C.c_int64), cs, ci]
+    # 8-bit rows: the arguments of the float calls
+    L.sift_hip_quantize.argtypes = [vp, vp, C.c_int64, vp, cs, ci]
+    L.sift_hip_result_copy_u8.argtypes = [vp, vp]
+    L.sift_hip_knn2_u8.argtypes = L.sift_hip_knn2.argtypes
+    L.sift_hip_match_u8.argtypes = L.sift_hip_match.argtypes
     _lib = L
     return L

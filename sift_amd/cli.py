@@ -3,6 +3,7 @@ overlay :59-76) on top of the GPU path — SURVEY.md §8(f) rows 1-3.
 
     python -m sift_amd.cli -i image.pgm [-s 1.6] [-k 1.41421354] [-o 4] [-d 3] [-p 0] [-r 1]
     python -m sift_amd.cli -i a.pgm --match b.pgm [--ratio 0.8] [--cross-check]      (an extension: matches.txt)
+    python -m sift_amd.cli -i a.pgm --match b.pgm --u8 [--verify ...]                (8-bit descriptors, integer distances)
     python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--iterations 2048] [--threshold 3] [--seed 0] [--refine 0] [--model homography|fundamental]   (... and inliers.txt)
     python -m sift_amd.cli -i a.pgm --match b.pgm --verify --guided [--guided-ratio R]   (... and guided.txt: the matches again, under the verified model)
 
@@ -145,11 +146,18 @@ def main(argv=None) -> int:
                     help="with --verify: match again under the winning model (a point competes only within --threshold pixels of it); "
                          "the matches go to guided.txt")
     ap.add_argument("--guided-ratio", type=float, default=None, help="ratio test of --guided (default: --ratio)")
+    ap.add_argument("--u8", action="store_true",
+                    help="with --match: quantise the descriptors to 8 bits on the GPU and match by the integer distance (the distances "
+                         "in matches.txt are integers)")
     args = ap.parse_args(argv)
     if args.verify and not args.match:
         ap.error("--verify needs --match")
     if args.guided and not args.verify:
         ap.error("--guided needs --verify")
+    if args.u8 and not args.match:
+        ap.error("--u8 needs --match")
+    if args.u8 and args.guided:
+        ap.error("--u8 cannot be combined with --guided: guided matching takes float descriptors only")
     if args.guided_ratio is not None and not args.guided:
         ap.error("--guided-ratio needs --guided")
     if args.model != "homography" and not args.verify:
@@ -176,10 +184,10 @@ def main(argv=None) -> int:
         if args.match:
             points2 = sift.calculate(_load(args.match))
             if not args.verify:
-                matches = sift.match(points, points2, args.ratio, args.cross_check)
+                matches = sift.match(points, points2, args.ratio, args.cross_check, args.u8)
             else:
                 matches, model, inlier = sift.verify(points, points2, args.ratio, args.cross_check, args.iterations, args.threshold, args.seed,
-                                                     args.refine, args.model)
+                                                     args.refine, args.model, args.u8)
             write_matches("matches.txt", matches)
             print(f"{len(points2)} interest points in {args.match}, {len(matches)} matches")
             if args.verify:

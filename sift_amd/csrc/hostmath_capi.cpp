@@ -157,6 +157,38 @@ void hostmath_match_knn2_guided(const float* q, const uint8_t* q_valid, const fl
     }
     delete[] on;
 }
+// 8-bit descriptors as include/sift_hip.h defines them ("8-bit descriptors and integer matching"): the quantiser, and
+// hostmath_match_knn2 over byte rows - d2 = sum (a[k] - b[k])^2 in int32, the same order rule, (float)d2 out.
+void hostmath_quantize(const float* desc, long long rows, uint8_t* out) {
+    for (long long i = 0; i < rows * 128; ++i) {
+        const float t = fmaf(desc[i], 255.0f, 0.5f);
+        out[i] = t >= 255.0f ? (uint8_t)255 : (t >= 0.0f ? (uint8_t)(int)t : (uint8_t)0);
+    }
+}
+void hostmath_match_knn2_u8(const uint8_t* q, const uint8_t* q_valid, long long nq, const uint8_t* t, const uint8_t* t_valid, long long nt,
+                            int32_t* idx, float* dist2) {
+    for (long long i = 0; i < nq; ++i) {
+        int32_t d1 = 0, d2 = 0, i1 = -1, i2 = -1;
+        if (!q_valid || q_valid[i]) {
+            for (long long j = 0; j < nt; ++j) {   // j ascending: a later row replaces an earlier one only when strictly nearer
+                if (t_valid && !t_valid[j]) continue;
+                int32_t d = 0;
+                for (int k = 0; k < 128; ++k) {
+                    const int32_t e = (int32_t)q[i * 128 + k] - (int32_t)t[j * 128 + k];
+                    d += e * e;
+                }
+                if (i1 < 0 || d < d1) {
+                    d2 = d1; i2 = i1; d1 = d; i1 = (int32_t)j;
+                } else if (i2 < 0 || d < d2) {
+                    d2 = d; i2 = (int32_t)j;
+                }
+            }
+        }
+        idx[2 * i] = i1; idx[2 * i + 1] = i2;
+        dist2[2 * i] = i1 < 0 ? INFINITY : (float)d1;
+        dist2[2 * i + 1] = i2 < 0 ? INFINITY : (float)d2;
+    }
+}
 // RANSAC homography as ransac_math.h defines it, in plain loops: what sift_hip_ransac_homography must reproduce bit for bit.
 void hostmath_ransac_draw(uint32_t seed, uint32_t set, uint32_t iteration, uint32_t m, uint32_t* idx) {
     uint32_t d[4];

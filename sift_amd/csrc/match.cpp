@@ -22,6 +22,7 @@ struct MatchState {
     ScratchBuf d_idx, d_dist;                // top-2 of every query row (forward rows first, then the cross-check's reverse rows)
     ScratchBuf d_seg, d_out, d_counts;       // records per pair segment, the dense list, per-pair counts
     ScratchBuf d_xy, d_models;               // guided matching: the rows' points (staged, or built from the keypoints), the pairs' models
+    ScratchBuf d_desc8;                      // 8-bit rows: staged from host memory, or quantised from the float rows (params->quantized)
     void* h_tables = nullptr;         // page-locked image of the three tables (the copy is asynchronous)
     size_t h_cap = 0;
     std::vector<int32_t> counts;
@@ -30,7 +31,7 @@ struct MatchState {
 void match_state_free(MatchState* st) {
     if (!st) return;
     for (ScratchBuf* b : {&st->d_desc, &st->d_kp, &st->d_norm, &st->d_valid, &st->d_tiles, &st->d_blocks, &st->d_pairs, &st->d_part, &st->d_idx,
-                   &st->d_dist, &st->d_seg, &st->d_out, &st->d_counts, &st->d_xy, &st->d_models})
+                   &st->d_dist, &st->d_seg, &st->d_out, &st->d_counts, &st->d_xy, &st->d_models, &st->d_desc8})
         b->release();
     if (st->h_tables) {
         ApiGuard api;
@@ -67,6 +68,8 @@ struct Job {
     const sift_hip_guide_params* guide = nullptr;
     const float* models = nullptr;
     float coord_scale = 1.0f;   // the result call's: 0.5f after a batch with subpixel
+    const uint8_t* desc8 = nullptr;   // sift_hip_knn2_u8 / sift_hip_match_u8: byte rows in place of `desc`
+    bool is_u8 = false;
 };
 
 int fail(const Job& j, const char* msg) {
@@ -118,10 +121,13 @@ int run(void* arg) {
     for (int s = 0; s < j.n_sets; ++s)
         if (j.offsets[s + 1] < j.offsets[s]) return fail(j, "sift_hip match: offsets must ascend");
     if (rows > 0x7fffffffLL / 2) return fail(j, "sift_hip match: too many rows");
-    if (rows > 0 && !j.desc) return fail(j, "sift_hip match: no descriptors");
-    bool use_ratio = false, cross = false;
+    if (rows > 0 && !(j.is_u8 ? (const void*)j.desc8 : (const void*)j.desc)) return fail(j, "sift_hip match: no descriptors");
+    bool use_ratio = false, cross = false, quantized = false;
     float ratio2 = 0.0f;
     if (j.params) {
+        if (j.params->quantized > 1) return fail(j, "sift_hip match: quantized must be 0 (float rows) or 1 (8-bit rows, integer distances)");
+        quantized = j.params->quantized == 1;
+        if (quantized && j.guided) return fail(j, "sift_hip match: quantized = 1 is not available in guided matching (float rows only)");
         const float r = j.params->ratio;
         if (!(r >= 0.0f && r <= 1.0f)) return fail(j, "sift_hip match: ratio must be 0 (no ratio test) or in (0, 1]");
         use_ratio = r != 0.0f;
@@ -158,9 +164,19 @@ int run(void* arg) {
 
     // ---- inputs on the device ----
     const float* d_desc = j.desc;
+    const uint8_t* d_desc8 = j.desc8;
     const sift_hip_keypoint* d_kp = j.kp;
     if (!j.inputs_on_device) {
-        if (!match_ptr_on_device(j.desc)) {
+        if (j.is_u8) {
+            if (!match_ptr_on_device(j.desc8)) {
+                st.d_desc8.ensure((size_t)rows * 128);
+                match_upload(j.c, st.d_desc8.p, j.desc8, (size_t)rows * 128);
+                match_wait(j.c);
+                d_desc8 = st.d_desc8.as<uint8_t>();
+            } else if (reinterpret_cast<uintptr_t>(j.desc8) % 16 != 0) {
+                return fail(j, "sift_hip match: 8-bit rows in device memory must be aligned to 16 bytes");
+            }
+        } else if (!match_ptr_on_device(j.desc)) {
             st.d_desc.ensure((size_t)rows * 128 * sizeof(float));
             match_upload(j.c, st.d_desc.p, j.desc, (size_t)rows * 128 * sizeof(float));
             match_wait(j.c);   // pageable memory travels through the context's two staging buffers: the next upload refills them
@@ -245,6 +261,11 @@ int run(void* arg) {
     SIFT_HIP_CHECK(hipMemcpyAsync(st.d_blocks.p, h + b_tiles, b_blocks, hipMemcpyHostToDevice, v.stream));
     SIFT_HIP_CHECK(hipMemcpyAsync(st.d_pairs.p, h + b_tiles + b_blocks, b_pairs, hipMemcpyHostToDevice, v.stream));
 
+    const bool u8 = j.is_u8 || quantized;
+    if (quantized && !j.is_u8) {   // the float rows become bytes on the device, in the pass that forms their norms
+        st.d_desc8.ensure((size_t)rows * 128);
+        d_desc8 = st.d_desc8.as<uint8_t>();
+    }
     st.d_norm.ensure((size_t)rows * sizeof(float));
     st.d_valid.ensure((size_t)rows);
     st.d_part.ensure(std::max<size_t>(tiles.size(), 1) * kMatchQ * sizeof(MatchTop2));
@@ -255,13 +276,22 @@ int run(void* arg) {
     float* d_dist = dist_direct ? j.dist2 : st.d_dist.as<float>();
 
     // ---- the launches: one of each kernel, whatever the number of pairs ----
-    launch_match_norms(v.stream, d_desc, d_kp, rows, st.d_norm.as<float>(), st.d_valid.as<uint8_t>());
-    if (j.guided)
-        launch_match_tiles_guided(v.stream, d_desc, st.d_norm.as<float>(), st.d_valid.as<uint8_t>(), st.d_tiles.as<MatchTile>(), (int)tiles.size(),
-                                  st.d_part.as<MatchTop2>(), (int)j.guide->model, ga);
-    else
-        launch_match_tiles(v.stream, d_desc, st.d_norm.as<float>(), st.d_valid.as<uint8_t>(), st.d_tiles.as<MatchTile>(), (int)tiles.size(),
-                           st.d_part.as<MatchTop2>());
+    if (u8) {
+        if (j.is_u8)
+            launch_match_norms_u8(v.stream, d_desc8, d_kp, rows, st.d_norm.as<int32_t>(), st.d_valid.as<uint8_t>());
+        else
+            launch_match_quantize_norms(v.stream, d_desc, d_kp, rows, st.d_desc8.as<uint8_t>(), st.d_norm.as<int32_t>(), st.d_valid.as<uint8_t>());
+        launch_match_tiles_u8(v.stream, d_desc8, st.d_norm.as<int32_t>(), st.d_valid.as<uint8_t>(), st.d_tiles.as<MatchTile>(), (int)tiles.size(),
+                              st.d_part.as<MatchTop2>());
+    } else {
+        launch_match_norms(v.stream, d_desc, d_kp, rows, st.d_norm.as<float>(), st.d_valid.as<uint8_t>());
+        if (j.guided)
+            launch_match_tiles_guided(v.stream, d_desc, st.d_norm.as<float>(), st.d_valid.as<uint8_t>(), st.d_tiles.as<MatchTile>(),
+                                      (int)tiles.size(), st.d_part.as<MatchTop2>(), (int)j.guide->model, ga);
+        else
+            launch_match_tiles(v.stream, d_desc, st.d_norm.as<float>(), st.d_valid.as<uint8_t>(), st.d_tiles.as<MatchTile>(), (int)tiles.size(),
+                               st.d_part.as<MatchTop2>());
+    }
     launch_match_merge(v.stream, st.d_part.as<MatchTop2>(), st.d_valid.as<uint8_t>(), st.d_blocks.as<MatchBlock>(), (int)blocks.size(), d_idx,
                        d_dist);
     SIFT_HIP_CHECK(hipGetLastError());
@@ -292,6 +322,45 @@ int run(void* arg) {
     if (j.total) *j.total = total;
     if (j.d_recs_out) *j.d_recs_out = d_out;
     if (j.host_counts_out) std::copy(st.counts.begin(), st.counts.end(), j.host_counts_out);
+    return SIFT_HIP_OK;
+}
+
+// sift_hip_quantize and sift_hip_result_copy_u8: float rows (caller memory, or the context's results) -> byte rows in caller memory
+struct QuantizeJob {
+    sift_hip_ctx* c;
+    const float* desc;
+    bool from_result;
+    long long rows;
+    uint8_t* out;
+    char* err;
+    int errlen;
+};
+
+int run_quantize(void* arg) {
+    const QuantizeJob& j = *static_cast<const QuantizeJob*>(arg);
+    MatchCtxView v = match_ctx_view(j.c);
+    SIFT_HIP_CHECK(hipSetDevice(v.device));
+    if (j.rows <= 0) return SIFT_HIP_OK;
+    const bool in_on_device = j.from_result || match_ptr_on_device(j.desc), direct = match_ptr_on_device(j.out);
+    if ((in_on_device && reinterpret_cast<uintptr_t>(j.desc) % 16 != 0) || (direct && reinterpret_cast<uintptr_t>(j.out) % 16 != 0)) {
+        match_set_err(j.err, j.errlen, "sift_hip quantize: rows in device memory must be aligned to 16 bytes");
+        return SIFT_HIP_EINVAL;
+    }
+    if (!*v.state) *v.state = new MatchState();
+    MatchState& st = **v.state;
+    const float* d_desc = j.desc;
+    if (!in_on_device) {
+        st.d_desc.ensure((size_t)j.rows * 128 * sizeof(float));
+        match_upload(j.c, st.d_desc.p, j.desc, (size_t)j.rows * 128 * sizeof(float));
+        match_wait(j.c);
+        d_desc = st.d_desc.as<float>();
+    }
+    if (!direct) st.d_desc8.ensure((size_t)j.rows * 128);
+    uint8_t* d_out = direct ? j.out : st.d_desc8.as<uint8_t>();
+    launch_match_quantize(v.stream, d_desc, j.rows, d_out);
+    SIFT_HIP_CHECK(hipGetLastError());
+    if (!direct) match_download(j.c, j.out, d_out, (size_t)j.rows * 128);
+    match_wait(j.c);
     return SIFT_HIP_OK;
 }
 
@@ -394,6 +463,45 @@ int sift_hip_result_match_guided(sift_hip_ctx* c, int n_pairs, const int32_t* pa
     if (!c) { match_set_err(err, errlen, "sift_hip_result_match_guided: no context (matching runs on the GPU only)"); return SIFT_HIP_EINVAL; }
     if (!params) { match_set_err(err, errlen, "sift_hip_result_match_guided: no parameters"); return SIFT_HIP_EINVAL; }
     return result_match_guided(c, n_pairs, pair_q, pair_t, params, guide, models, recs, counts, total, err, errlen);
+}
+
+int sift_hip_quantize(sift_hip_ctx* c, const float* desc, int64_t rows, uint8_t* out, char* err, int errlen) {
+    if (!c) { match_set_err(err, errlen, "sift_hip_quantize: no context (the quantiser runs on the GPU only)"); return SIFT_HIP_EINVAL; }
+    if (rows < 0 || rows > 0x7fffffffLL / 2) { match_set_err(err, errlen, "sift_hip_quantize: bad number of rows"); return SIFT_HIP_EINVAL; }
+    if (rows > 0 && (!desc || !out)) { match_set_err(err, errlen, "sift_hip_quantize: no rows or no result array"); return SIFT_HIP_EINVAL; }
+    QuantizeJob j{c, desc, false, (long long)rows, out, err, errlen};
+    return match_guarded(err, errlen, run_quantize, &j);
+}
+
+int sift_hip_result_copy_u8(sift_hip_ctx* c, uint8_t* descriptors) {
+    if (!c) return SIFT_HIP_EINVAL;
+    const MatchCtxView v = match_ctx_view(c);
+    if (!v.have_result) return SIFT_HIP_EINVAL;
+    long long total = 0;
+    for (int i = 0; i < v.n_images; ++i) total += v.counts[i];
+    if (total <= 0 || !descriptors) return SIFT_HIP_OK;
+    QuantizeJob j{c, v.d_desc, true, total, descriptors, nullptr, 0};
+    return match_guarded(nullptr, 0, run_quantize, &j);
+}
+
+int sift_hip_knn2_u8(sift_hip_ctx* c, const uint8_t* desc, const sift_hip_keypoint* kp, int n_sets, const int64_t* offsets, int n_pairs,
+                     const int32_t* pair_q, const int32_t* pair_t, int32_t* idx, float* dist2, char* err, int errlen) {
+    if (!c) { match_set_err(err, errlen, "sift_hip_knn2_u8: no context (matching runs on the GPU only)"); return SIFT_HIP_EINVAL; }
+    Job j{c, nullptr, kp, false, n_sets, offsets, n_pairs, pair_q, pair_t, nullptr, idx, dist2, nullptr, nullptr, nullptr, err, errlen};
+    j.desc8 = desc;
+    j.is_u8 = true;
+    return match_guarded(err, errlen, run, &j);
+}
+
+int sift_hip_match_u8(sift_hip_ctx* c, const uint8_t* desc, const sift_hip_keypoint* kp, int n_sets, const int64_t* offsets, int n_pairs,
+                      const int32_t* pair_q, const int32_t* pair_t, const sift_hip_match_params* params, sift_hip_match_rec* recs,
+                      int32_t* counts, int64_t* total, char* err, int errlen) {
+    if (!c) { match_set_err(err, errlen, "sift_hip_match_u8: no context (matching runs on the GPU only)"); return SIFT_HIP_EINVAL; }
+    if (!params) { match_set_err(err, errlen, "sift_hip_match_u8: no parameters"); return SIFT_HIP_EINVAL; }
+    Job j{c, nullptr, kp, false, n_sets, offsets, n_pairs, pair_q, pair_t, params, nullptr, nullptr, recs, counts, total, err, errlen};
+    j.desc8 = desc;
+    j.is_u8 = true;
+    return match_guarded(err, errlen, run, &j);
 }
 
 }  // extern "C"

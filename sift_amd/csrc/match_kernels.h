@@ -58,6 +58,18 @@ void launch_match_pack(hipStream_t s, const sift_hip_match_rec* d_seg, const Mat
                        sift_hip_match_rec* d_out);
 void tu_touch_match(hipStream_t s);
 
+// ---- 8-bit rows (kernels_match_u8.hip; include/sift_hip.h, "8-bit descriptors and integer matching") ----------
+// the quantiser alone: rows x 128 floats -> rows x 128 bytes (both 16-byte aligned)
+void launch_match_quantize(hipStream_t s, const float* d_desc, long long rows, uint8_t* d_out);
+// n'(a) = sum (a[k] - 128)^2 and the valid flag of every byte row
+void launch_match_norms_u8(hipStream_t s, const uint8_t* d_desc8, const sift_hip_keypoint* d_kp, long long rows, int32_t* d_norm, uint8_t* d_valid);
+// both in one pass over float rows: d_desc8 receives the bytes
+void launch_match_quantize_norms(hipStream_t s, const float* d_desc, const sift_hip_keypoint* d_kp, long long rows, uint8_t* d_desc8,
+                                 int32_t* d_norm, uint8_t* d_valid);
+// the tile kernel on the i8 matrix instruction: the tables and the partials of launch_match_tiles, distances as (float)d2
+void launch_match_tiles_u8(hipStream_t s, const uint8_t* d_desc8, const int32_t* d_norm, const uint8_t* d_valid, const MatchTile* d_tiles,
+                           int n_tiles, MatchTop2* d_part);
+
 // scratch of the matcher and of the geometric verification (ransac.cpp): device memory that only grows, kept with the context
 struct ScratchBuf {
     void* p = nullptr;

@@ -180,6 +180,19 @@ class Context:
             raise HipError("sift_hip_result_copy failed")
         return kp, desc
 
+    def results_u8(self, kp_out=None, desc_out=None):
+        """(keypoints, descriptors [total, 128] uint8): results() with the descriptors quantised to 8 bits on the GPU
+        (sift_hip_result_copy_u8; include/sift_hip.h, "8-bit descriptors and integer matching") - 128 instead of 512 bytes per
+        keypoint cross the link.  `kp_out` / `desc_out` as for results()."""
+        t = max(self.total(), 0)
+        kp = np.zeros(t, _lib.KEYPOINT_DTYPE) if kp_out is None else kp_out.reshape(-1)[:t]
+        desc = np.zeros((t, 128), np.uint8) if desc_out is None else desc_out.reshape(-1, 128)[:t]
+        if kp.size < t or desc.shape[0] < t or desc.dtype != np.uint8:
+            raise ValueError("result arrays too small, or descriptors not uint8")
+        if t > 0 and (self._L.sift_hip_result_copy(self._h, kp.ctypes.data, None) or self._L.sift_hip_result_copy_u8(self._h, desc.ctypes.data)):
+            raise HipError("sift_hip_result_copy_u8 failed")
+        return kp, desc
+
     def results_sparse(self, rec_out=None, val_out=None):
         """The results in the sparse wire format, in host memory: (records uint8 [total, 34] = 20-byte keypoint record + 112
         presence bits, values float32 [n] = the descriptor floats that are not +0.0f) - what crosses the link is ~200 instead of
@@ -367,15 +380,18 @@ class Context:
         """sift_hip_knn2: top-2 of every query row of every pair -> (idx [rows, 2] int32, dist2 [rows, 2] float32), rows = the
         pairs' query rows in pair order.  `desc` / `kp`: numpy arrays, tensors or addresses (host or device memory); `idx_out` /
         `dist_out`: where the result goes instead of new numpy arrays (returned as given)."""
+        return self._knn2_sets(self._L.sift_hip_knn2, np.float32, desc, offsets, pairs, kp, idx_out, dist_out)
+
+    def _knn2_sets(self, call, dtype, desc, offsets, pairs, kp, idx_out, dist_out):
         offsets = np.ascontiguousarray(offsets, np.int64)
         pq, pt = self._pairs(pairs)
         rows = int(sum(offsets[q + 1] - offsets[q] for q in pq if 0 <= q < offsets.size - 1))
         idx = np.full((rows, 2), -1, np.int32) if idx_out is None else idx_out
         dist = np.full((rows, 2), np.inf, np.float32) if dist_out is None else dist_out
         if isinstance(desc, np.ndarray):
-            desc = np.ascontiguousarray(desc, np.float32)
+            desc = self._rows(desc, dtype)
         err = C.create_string_buffer(512)
-        rc = self._L.sift_hip_knn2(self._h, self._addr(desc), self._addr(kp), offsets.size - 1, offsets, pq.size, pq, pt,
+        rc = call(self._h, self._addr(desc), self._addr(kp), offsets.size - 1, offsets, pq.size, pq, pt,
                                    self._addr(idx), self._addr(dist), err, 512)
         if rc:
             _raise(rc, err)
@@ -388,6 +404,13 @@ class Context:
         t = np.ascontiguousarray(t, np.float32).reshape(-1, 128)
         desc, offsets, kp = self._two_sets(q, t, q_kp, t_kp)
         return self.knn2_sets(desc, offsets, [(0, 1)], kp)
+
+    @staticmethod
+    def _rows(desc, dtype):
+        """A numpy array as contiguous rows of `dtype`; byte rows must arrive as uint8 (no silent conversion of floats)."""
+        if dtype == np.uint8 and desc.dtype != np.uint8:
+            raise ValueError("8-bit matching: the rows must be uint8 (Context.quantize makes them)")
+        return np.ascontiguousarray(desc, dtype)
 
     @staticmethod
     def _two_sets(q, t, q_kp, t_kp):
@@ -403,10 +426,14 @@ class Context:
                 kp[q.shape[0]:] = t_kp
         return desc, offsets, kp
 
-    def match_sets(self, desc, offsets, pairs, ratio=0.8, cross_check=False, kp=None, recs_out=None):
+    def match_sets(self, desc, offsets, pairs, ratio=0.8, cross_check=False, kp=None, recs_out=None, quantized=False):
         """sift_hip_match: the filtered matches of every pair -> (records, counts): records (query, train, dist2, second2) in
         pair order, then query order; counts[p] of them belong to pair p.  `recs_out`: a tensor / address with room for one
-        record per query row (then the first element returned is the total instead of an array)."""
+        record per query row (then the first element returned is the total instead of an array).  `quantized`: the float rows
+        are quantised to 8 bits on the device and matched by the integer distance (match_sets_u8 of quantize(desc))."""
+        return self._match_sets(self._L.sift_hip_match, np.float32, desc, offsets, pairs, ratio, cross_check, kp, recs_out, quantized)
+
+    def _match_sets(self, call, dtype, desc, offsets, pairs, ratio, cross_check, kp, recs_out, quantized):
         offsets = np.ascontiguousarray(offsets, np.int64)
         pq, pt = self._pairs(pairs)
         rows = int(sum(offsets[q + 1] - offsets[q] for q in pq if 0 <= q < offsets.size - 1))
@@ -414,31 +441,82 @@ class Context:
         counts = np.zeros(pq.size, np.int32)
         total = C.c_int64()
         if isinstance(desc, np.ndarray):
-            desc = np.ascontiguousarray(desc, np.float32)
-        prm = _lib.MatchParams(float(ratio), 1 if cross_check else 0)
+            desc = self._rows(desc, dtype)
+        prm = _lib.MatchParams(float(ratio), 1 if cross_check else 0, self._quantized(quantized))
         err = C.create_string_buffer(512)
-        rc = self._L.sift_hip_match(self._h, self._addr(desc), self._addr(kp), offsets.size - 1, offsets, pq.size, pq, pt, C.byref(prm),
+        rc = call(self._h, self._addr(desc), self._addr(kp), offsets.size - 1, offsets, pq.size, pq, pt, C.byref(prm),
                                     self._addr(recs), counts, C.byref(total), err, 512)
         if rc:
             _raise(rc, err)
         return (recs[:total.value] if recs_out is None else int(total.value)), counts
 
-    def match(self, q, t, ratio=0.8, cross_check=False, q_kp=None, t_kp=None):
-        """Matches of the rows of `q` among `t` (numpy, host memory): records (query, train, dist2, second2) in query order."""
+    def match(self, q, t, ratio=0.8, cross_check=False, q_kp=None, t_kp=None, quantized=False):
+        """Matches of the rows of `q` among `t` (numpy, host memory): records (query, train, dist2, second2) in query order.
+        `quantized` as for match_sets."""
         q = np.ascontiguousarray(q, np.float32).reshape(-1, 128)
         t = np.ascontiguousarray(t, np.float32).reshape(-1, 128)
         desc, offsets, kp = self._two_sets(q, t, q_kp, t_kp)
-        return self.match_sets(desc, offsets, [(0, 1)], ratio, cross_check, kp)[0]
+        return self.match_sets(desc, offsets, [(0, 1)], ratio, cross_check, kp, quantized=quantized)[0]
 
-    def match_images(self, pairs, ratio=0.8, cross_check=False):
-        """sift_hip_result_match: matches between images of the last batch, on the device-resident results -> (records, counts)."""
+    # ---- 8-bit rows (include/sift_hip.h, "8-bit descriptors and integer matching") -----------------------------
+    @staticmethod
+    def _quantized(quantized):
+        """The byte of sift_hip_match_params: False / True, or a number the call itself judges (above 1: ValueError)."""
+        q = int(quantized)
+        if not 0 <= q <= 255:
+            raise ValueError("quantized must be False or True")
+        return q
+
+    def quantize(self, desc, out=None):
+        """sift_hip_quantize: float rows [n, 128] -> uint8 rows [n, 128], q(v) = trunc(fmaf(v, 255, 0.5)) clamped to 0 .. 255.
+        `desc`: a numpy array, a tensor or an address; `out`: where the bytes go instead of a new numpy array (a tensor or an
+        address needs `rows`-sized room; returned as given)."""
+        if isinstance(desc, np.ndarray):
+            desc = np.ascontiguousarray(desc, np.float32).reshape(-1, 128)
+            rows = desc.shape[0]
+        elif hasattr(desc, "numel"):
+            rows = int(desc.numel()) // 128
+        else:
+            raise ValueError("quantize: a numpy array or a tensor (use the C call for a plain address)")
+        res = np.zeros((rows, 128), np.uint8) if out is None else out
+        err = C.create_string_buffer(512)
+        rc = self._L.sift_hip_quantize(self._h, self._addr(desc), rows, self._addr(res), err, 512)
+        if rc:
+            _raise(rc, err)
+        return res
+
+    def knn2_sets_u8(self, desc, offsets, pairs, kp=None, idx_out=None, dist_out=None):
+        """sift_hip_knn2_u8: knn2_sets over uint8 rows; the distances are the exact integers sum (a - b)^2 as float32."""
+        return self._knn2_sets(self._L.sift_hip_knn2_u8, np.uint8, desc, offsets, pairs, kp, idx_out, dist_out)
+
+    def knn2_u8(self, q, t, q_kp=None, t_kp=None):
+        """knn2 over uint8 rows `q` [nq, 128] and `t` [nt, 128] (numpy, host memory)."""
+        q = self._rows(np.asarray(q), np.uint8).reshape(-1, 128)
+        t = self._rows(np.asarray(t), np.uint8).reshape(-1, 128)
+        desc, offsets, kp = self._two_sets(q, t, q_kp, t_kp)
+        return self.knn2_sets_u8(desc, offsets, [(0, 1)], kp)
+
+    def match_sets_u8(self, desc, offsets, pairs, ratio=0.8, cross_check=False, kp=None, recs_out=None):
+        """sift_hip_match_u8: match_sets over uint8 rows."""
+        return self._match_sets(self._L.sift_hip_match_u8, np.uint8, desc, offsets, pairs, ratio, cross_check, kp, recs_out, False)
+
+    def match_u8(self, q, t, ratio=0.8, cross_check=False, q_kp=None, t_kp=None):
+        """match over uint8 rows (numpy, host memory): records in query order."""
+        q = self._rows(np.asarray(q), np.uint8).reshape(-1, 128)
+        t = self._rows(np.asarray(t), np.uint8).reshape(-1, 128)
+        desc, offsets, kp = self._two_sets(q, t, q_kp, t_kp)
+        return self.match_sets_u8(desc, offsets, [(0, 1)], ratio, cross_check, kp)[0]
+
+    def match_images(self, pairs, ratio=0.8, cross_check=False, quantized=False):
+        """sift_hip_result_match: matches between images of the last batch, on the device-resident results -> (records, counts).
+        `quantized`: over the results' descriptors quantised to 8 bits (match_sets_u8 of results_u8())."""
         pq, pt = self._pairs(pairs)
         cnt = self.counts() if self._L.sift_hip_result_images(self._h) >= 0 else np.zeros(0, np.int32)   # none: the call says so
         rows = int(sum(cnt[q] for q in pq if 0 <= q < cnt.size))
         recs = np.zeros(rows, _lib.MATCH_DTYPE)
         counts = np.zeros(pq.size, np.int32)
         total = C.c_int64()
-        prm = _lib.MatchParams(float(ratio), 1 if cross_check else 0)
+        prm = _lib.MatchParams(float(ratio), 1 if cross_check else 0, self._quantized(quantized))
         err = C.create_string_buffer(512)
         rc = self._L.sift_hip_result_match(self._h, pq.size, pq, pt, C.byref(prm), C.c_void_p(recs.ctypes.data), counts, C.byref(total), err, 512)
         if rc:
@@ -496,9 +574,9 @@ class Context:
         return self.knn2_guided_sets(desc, xy, offsets, [(0, 1)], np.asarray(model_matrix, np.float32).reshape(1, 9), model, threshold, kp)
 
     def match_guided_sets(self, desc, xy, offsets, pairs, models, model="homography", threshold=3.0, ratio=0.8, cross_check=False, kp=None,
-                          recs_out=None):
+                          recs_out=None, quantized=False):
         """sift_hip_match_guided: match_sets under the pairs' models -> (records, counts).  Arguments as for knn2_guided_sets and
-        match_sets."""
+        match_sets.  Guided matching takes float rows only: `quantized=True` is a ValueError (the call says so)."""
         offsets = np.ascontiguousarray(offsets, np.int64)
         pq, pt = self._pairs(pairs)
         rows = int(sum(offsets[q + 1] - offsets[q] for q in pq if 0 <= q < offsets.size - 1))
@@ -509,7 +587,7 @@ class Context:
             desc = np.ascontiguousarray(desc, np.float32)
         if isinstance(xy, np.ndarray):
             xy = np.ascontiguousarray(xy, np.float32)
-        mprm = _lib.MatchParams(float(ratio), 1 if cross_check else 0)
+        mprm = _lib.MatchParams(float(ratio), 1 if cross_check else 0, self._quantized(quantized))
         gprm = self._guide(model, threshold)
         models = self._models9(models, pq.size)
         err = C.create_string_buffer(512)
@@ -529,16 +607,17 @@ class Context:
         return self.match_guided_sets(desc, xy, offsets, [(0, 1)], np.asarray(model_matrix, np.float32).reshape(1, 9), model, threshold, ratio,
                                       cross_check, kp)[0]
 
-    def match_images_guided(self, pairs, models, model="homography", threshold=3.0, ratio=0.8, cross_check=False):
+    def match_images_guided(self, pairs, models, model="homography", threshold=3.0, ratio=0.8, cross_check=False, quantized=False):
         """sift_hip_result_match_guided: match_images under the pairs' models, e.g. those verify_images returned, on the
-        device-resident results (the keypoints' image coordinates are built on the GPU) -> (records, counts)."""
+        device-resident results (the keypoints' image coordinates are built on the GPU) -> (records, counts).  `quantized=True`
+        is a ValueError, as for match_guided_sets."""
         pq, pt = self._pairs(pairs)
         cnt = self.counts() if self._L.sift_hip_result_images(self._h) >= 0 else np.zeros(0, np.int32)   # none: the call says so
         rows = int(sum(cnt[q] for q in pq if 0 <= q < cnt.size))
         recs = np.zeros(rows, _lib.MATCH_DTYPE)
         counts = np.zeros(pq.size, np.int32)
         total = C.c_int64()
-        mprm = _lib.MatchParams(float(ratio), 1 if cross_check else 0)
+        mprm = _lib.MatchParams(float(ratio), 1 if cross_check else 0, self._quantized(quantized))
         gprm = self._guide(model, threshold)
         models = self._models9(models, pq.size)
         err = C.create_string_buffer(512)
@@ -626,11 +705,12 @@ class Context:
             _raise(rc, err)
         return models, inlier
 
-    def verify_images(self, pairs, ratio=0.8, cross_check=False, iterations=2048, threshold=3.0, seed=0, refine=0, model="homography"):
+    def verify_images(self, pairs, ratio=0.8, cross_check=False, iterations=2048, threshold=3.0, seed=0, refine=0, model="homography",
+                      quantized=False):
         """sift_hip_result_verify: match_images followed by ransac_homography on the matches' image coordinates, all on the
         device-resident results -> (records, counts, models, inlier): models[p] belongs to pair p, inlier[i] to records[i].
         `refine` as for ransac_homography.  model="fundamental": sift_hip_result_verify_fundamental, ransac_fundamental in
-        place of ransac_homography (models of FUNDAMENTAL_DTYPE; `refine` must be 0)."""
+        place of ransac_homography (models of FUNDAMENTAL_DTYPE; `refine` must be 0).  `quantized` as for match_images."""
         if model not in ("homography", "fundamental"):
             raise ValueError('verify_images: model must be "homography" or "fundamental"')
         fund = model == "fundamental"
@@ -642,7 +722,7 @@ class Context:
         models = np.zeros(pq.size, _lib.FUNDAMENTAL_DTYPE if fund else _lib.HOMOGRAPHY_DTYPE)
         counts = np.zeros(pq.size, np.int32)
         total = C.c_int64()
-        mprm = _lib.MatchParams(float(ratio), 1 if cross_check else 0)
+        mprm = _lib.MatchParams(float(ratio), 1 if cross_check else 0, self._quantized(quantized))
         rprm = _lib.RansacParams(int(iterations) & 0xffffffff, int(seed) & 0xffffffff, float(threshold), int(refine) & 0xffffffff)
         err = C.create_string_buffer(512)
         call = self._L.sift_hip_result_verify_fundamental if fund else self._L.sift_hip_result_verify
@@ -821,9 +901,10 @@ class Sift:
         kp, desc = self.ctx.results()
         return self.ctx.counts(), kp, desc
 
-    def match(self, points_a, points_b, ratio: float = 0.8, cross_check: bool = False):
+    def match(self, points_a, points_b, ratio: float = 0.8, cross_check: bool = False, quantized: bool = False):
         """Matches between two InterestPoint lists (an extension: the reference has no matcher) -> records (query, train,
-        dist2, second2), indices into the lists.  A point without a 128-float descriptor is an invalid row."""
+        dist2, second2), indices into the lists.  A point without a 128-float descriptor is an invalid row.  `quantized`: the
+        descriptors are quantised to 8 bits on the GPU and matched by the integer distance (dist2 / second2 are integers)."""
         def rows(points):
             d = np.zeros((len(points), 128), np.float32)
             kp = np.zeros(len(points), _lib.KEYPOINT_DTYPE)
@@ -834,10 +915,10 @@ class Sift:
             return d, kp
         qa, ka = rows(points_a)
         qb, kb = rows(points_b)
-        return self.ctx.match(qa, qb, ratio, cross_check, ka, kb)
+        return self.ctx.match(qa, qb, ratio, cross_check, ka, kb, quantized)
 
     def verify(self, points_a, points_b, ratio: float = 0.8, cross_check: bool = False, iterations: int = 2048, threshold: float = 3.0,
-               seed: int = 0, refine: int = 0, model: str = "homography"):
+               seed: int = 0, refine: int = 0, model: str = "homography", quantized: bool = False):
         """match() followed by the geometric check of its list (an extension) -> (records, model, inlier): the best four-point
         homography from image a to image b over the matches' image coordinates (loc * 2^octave, halved with subpixel), as one
         record (h [9] row-major, inliers, iteration; -1: none, refined), and one flag per record.  `refine`: rounds of
@@ -846,7 +927,7 @@ class Sift:
         right model for two views of a general scene, where a homography explains one plane only.  `refine` must then be 0."""
         if model not in ("homography", "fundamental"):
             raise ValueError('verify: model must be "homography" or "fundamental"')
-        recs = self.match(points_a, points_b, ratio, cross_check)
+        recs = self.match(points_a, points_b, ratio, cross_check, quantized)
         scale = np.float32(0.5 if self.subpixel else 1.0)
 
         def coords(points, which):

@@ -19,6 +19,12 @@ models, sift_hip_result_match alternates with sift_hip_result_match_guided under
 (3) a band of 3 px under a fixed model (nearly every candidate is inadmissible, a lane's second best stays +inf for long).  The
 frames of the bench batch are unrelated, so (1) is a narrow band too.  Median, min and max of --reps; lines are appended to
 --out.  --unguided-only: the unguided calls of those cases alone (for an A/B of two builds, SIFT_HIP_LIBRARY).
+
+--u8-arm: 8-bit descriptors and integer matching beside the float matcher (no torch arm), alternating in the same run: the top-2
+of case (a) on device-resident rows (sift_hip_knn2 on the float results against sift_hip_knn2_u8 on their bytes), and case (b)
+without and with the cross-check (sift_hip_result_match with quantized = 0 against quantized = 1, which includes the quantiser's
+pass).  256 sampled query rows of (a) are compared bit for bit with the integer host checker.  Median, min and max of --reps, the
+ratio of the medians, and whether the two min - max intervals overlap (then there is no winner); lines are appended to --out.
 """
 import argparse
 import json
@@ -46,6 +52,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--guided-arm", action="store_true")
     ap.add_argument("--unguided-only", action="store_true")
+    ap.add_argument("--u8-arm", action="store_true")
     args = ap.parse_args()
 
     import torch
@@ -126,17 +133,54 @@ def main():
                 emit({"case": "guided, " + name, "cross_check": cross, "pairs_with_a_verified_model": found,
                       "matches": {k: int(fn()[0].size) for k, fn in arms.items()}, **res})
 
+    def u8_arms(ctx, cnt):
+        import match_u8_ref as U
+        n = cnt.size
+        off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+        d_kp, d_desc = ctx.result_device_ptrs()
+        kp, d8 = ctx.results_u8()
+        t8 = torch.from_numpy(d8).cuda()
+        nq, nt = int(cnt[0]), int(cnt[1])
+        idx = torch.zeros((nq, 2), dtype=torch.int32, device="cuda")
+        dist = torch.zeros((nq, 2), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+
+        def verdict(res):
+            f, u = res["f32"], res["u8"]
+            overlap = not (u["max_ms"] < f["min_ms"] or f["max_ms"] < u["min_ms"])
+            return {"f32_over_u8_medians": round(f["median_ms"] / u["median_ms"], 2), "intervals_overlap": overlap}
+
+        res = timed({"f32": lambda: ctx.knn2_sets(d_desc, off, [(0, 1)], d_kp, idx, dist),
+                     "u8": lambda: ctx.knn2_sets_u8(t8, off, [(0, 1)], d_kp, idx, dist)})
+        rows = np.random.default_rng(0).choice(nq, size=min(256, nq), replace=False)
+        v = kp["has_descriptor"]
+        want = U.knn2(d8[off[0]:off[1]][rows], d8[off[1]:off[2]], v[off[0]:off[1]][rows], v[off[1]:off[2]])
+        ok = M.same_bits(idx.cpu().numpy()[rows], want[0]) and M.same_bits(dist.cpu().numpy()[rows], want[1])
+        emit({"case": "u8 arm, a: frames 1 and 2 of the bench batch, top-2 on device-resident rows", "nq": nq, "nt": nt,
+              "spot_check_256_rows_bitwise": bool(ok), **res, **verdict(res)})
+        pairs = [(i, i + 1) for i in range(n - 1)]
+        for cross in (False, True):
+            arms = {"f32": lambda: ctx.match_images(pairs, 0.8, cross), "u8": lambda: ctx.match_images(pairs, 0.8, cross, quantized=True)}
+            res = timed(arms)
+            emit({"case": f"u8 arm, b: the {len(pairs)} consecutive pairs in one sift_hip_result_match call (ratio 0.8)", "cross_check": cross,
+                  "matches": {k: int(fn()[0].size) for k, fn in arms.items()}, **res, **verdict(res)})
+
     ctx = Context(0)
     # ---- (a) and (b): the bench batch ----
     n = args.frames
     ctx.calculate_batch(synth_batch(n, 1920, 1080), _lib.Params(3, 4, 1.6, K_SQRT2, 0))
     cnt = ctx.counts()
-    if args.guided_arm or args.unguided_only:
-        guided_arms(ctx, cnt)
+    if args.guided_arm or args.unguided_only or args.u8_arm:
+        if args.u8_arm:
+            u8_arms(ctx, cnt)
+        else:
+            guided_arms(ctx, cnt)
         ctx.close()
         if args.out:
             with open(args.out, "a") as f:
-                f.write("# tools/match_bench.py --guided-arm: sift_hip_result_match alternating with sift_hip_result_match_guided (ms on the host around each call)\n"
+                f.write("# tools/match_bench.py --u8-arm: the float matcher alternating with the 8-bit integer matcher (ms on the host around each call)\n"
+                        if args.u8_arm else
+                        "# tools/match_bench.py --guided-arm: sift_hip_result_match alternating with sift_hip_result_match_guided (ms on the host around each call)\n"
                         if args.guided_arm else "# tools/match_bench.py --unguided-only\n")
                 f.write("\n".join(lines) + "\n")
         return
