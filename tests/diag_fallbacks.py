@@ -19,8 +19,19 @@ import oracle_lib as O
 from sift_amd import _lib
 from sift_amd.synthetic import synth_frame
 from test_gpu_parity import CASES, CONVOLVE_SIGMAS, REDUCE_CASES, compare_run, convolve_cases
+from test_scale_steps_host import ROWS, populations, row_image, row_run
 
 pytestmark = pytest.mark.gpu
+
+MANY_LEVELS = "200x150 3x3 s1.0 k1.8"    # a plan with three gradient levels, octave 0's top level among them (tests/test_scale_steps_host.py)
+
+
+def compare_many_levels(ctx, report_dir, what, frames=1):
+    """The many-level row through compare_run; the levels the library's keypoints populate must be the row's."""
+    dogs, octaves, sigma, k, subpixel, final, levels = ROWS[MANY_LEVELS][4:]
+    rep = compare_run(ctx, row_image(MANY_LEVELS), dogs, octaves, subpixel, f"{MANY_LEVELS} [{what}]", report_dir, batch_of=frames, sigma=sigma, k=k,
+                      run=row_run(MANY_LEVELS))
+    assert rep["final"] == final and populations(ctx.stage("final", frames - 1), dogs, octaves, sigma, k) == levels
 
 
 def test_this_is_the_diag_library(ctx):
@@ -53,6 +64,7 @@ def test_two_pass_blur_operator(ctx):
 def test_two_pass_blur_pipeline(ctx, report_dir):
     with forced(ctx, fused_blur=0):
         compare_run(ctx, synth_frame(200, 160, 2), 3, 2, False, "two-pass blur 200x160", report_dir)
+        compare_many_levels(ctx, report_dir, "fused_blur = 0")
 
 
 def test_separate_scan_and_edge_filter(ctx, report_dir):
@@ -76,11 +88,15 @@ def test_streaming_decimating_blur(ctx, report_dir, case):
         compare_run(ctx, synth_frame(w, h, seed), 3, octaves, False, name + " [reduce_kept = 0]", report_dir, batch_of=frames)
 
 
-@pytest.mark.parametrize("case", [CASES[1], CASES[2], CASES[4]], ids=[CASES[1][0], CASES[2][0], CASES[4][0]])
+@pytest.mark.parametrize("case", [CASES[1], CASES[2], CASES[4], MANY_LEVELS], ids=[CASES[1][0], CASES[2][0], CASES[4][0], MANY_LEVELS])
 @pytest.mark.parametrize("streaming", [0, 1], ids=["tile", "streaming"])
 def test_dog_levels_written_by_the_pyramid(ctx, report_dir, case, streaming):
     """Every blur launch writes its DoG level (rounds 1 - 4's form; what a plan with a scanned octave whose rows are not
     16-byte aligned gets), the fused scan reads three DoG levels: levels, stage lists, descriptors."""
+    if case == MANY_LEVELS:
+        with forced(ctx, dog_in_extrema=0, stream_min_waves=streaming):
+            compare_many_levels(ctx, report_dir, "dog_in_extrema = 0", frames=2)
+        return
     name, w, h, seed, dogs, octaves, subpixel = case
     with forced(ctx, dog_in_extrema=0, stream_min_waves=streaming):
         rep = compare_run(ctx, synth_frame(w, h, seed), dogs, octaves, subpixel, name + " [dog_in_extrema = 0]", report_dir, batch_of=2)
@@ -91,6 +107,7 @@ def test_host_glue_path(ctx, report_dir):
     """flags down, libstdc++'s std::sort on the host, lists up (sift.cpp:37-54)"""
     with forced(ctx, gpu_cleanup=0):
         compare_run(ctx, synth_frame(333, 257, 9), 3, 3, False, "host-glue path 333x257", report_dir)
+        compare_many_levels(ctx, report_dir, "gpu_cleanup = 0")
 
 
 def test_host_glue_path_with_some_images_throwing(ctx):

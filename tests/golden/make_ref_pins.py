@@ -4,6 +4,7 @@
     python tests/golden/make_ref_pins.py                                   (in the build container, where /root/reference is mounted)
     python tests/golden/make_ref_pins.py bench_frame | config2 | truncation | configs | config5   (the long-running pins, one fixture each)
     python tests/golden/make_ref_pins.py hard_frames                       (HARD_CASES -> refpin_hard_frames.npz; refpin.npz is not rewritten)
+    python tests/golden/make_ref_pins.py scale_steps                       (SCALE_CASES -> refpin_scale_steps.npz; refpin.npz is not rewritten)
 
 /root/reference/bin/arch_x64/sift cannot be started here (Vigra, OpenCV, Boost are DT_NEEDED and absent) and the
 sources cannot be rebuilt for the same reason, but `Sift::calculate` and the `sift::alg` functions inside it only need
@@ -61,6 +62,13 @@ HARD_CASES = {
     "mirror4_160x120_3x2": (("hard", "mirror4", 160, 120), 3, 2, 0),
 }
 HARD_PIN = os.path.join(HERE, "refpin_hard_frames.npz")
+# Scale steps other than sqrt(2), where keypoints take their gradient maps from several Gaussian levels (sift.cpp:205-218;
+# tests/test_scale_steps_host.py): name -> (image spec, dogs, octaves, subpixel, sigma, k), a fixture of their own, same keys
+SCALE_CASES = {
+    "synth_160x120_5x2_s0.8_k1.5": (("synth", 160, 120, 1), 5, 2, 0, 0.8, 1.5),      # levels (0,0), (0,2), (0,3), (0,4)
+    "synth_200x150_3x3_s1.0_k1.8": (("synth", 200, 150, 3), 3, 3, 0, 1.0, 1.8),      # levels (0,0), (0,2) and octave 0's top level (0,3)
+}
+SCALE_PIN = os.path.join(HERE, "refpin_scale_steps.npz")
 BLUR_SIGMAS = [0.3, 1.0, 1.6, 2.0, 2.2627418, 3.2, 4.5254836, 6.4]
 BLUR_IMAGES = [("synth", 200, 150, 3), ("synth", 67, 131, 4), ("synth", 64, 64, 5)]
 PARABOLAS = [(3, 1.5, 4, 2.5, 5, 1.0), (0, 0.25, 1, 0.75, 2, 0.5), (34, 12.0, 35, 12.0, 0, 3.0), (10, 1.0, 11, 1.0, 12, 1.0)]
@@ -82,13 +90,14 @@ def refexec(*args):
     return r.returncode, r.stdout, r.stderr
 
 
-def ref_calculate(img, dogs, octaves, subpixel, tmp):
+def ref_calculate(img, dogs, octaves, subpixel, tmp, sigma=1.6, k=K_SQRT2):
     """-> dict with what the reference returned (or its exception text)."""
+    sigma, k = repr(float(np.float32(sigma))), repr(float(np.float32(k)))
     h, w = img.shape
     src = os.path.join(tmp, "in.f32")
     img.astype(np.float32).tofile(src)
     out = os.path.join(tmp, "out")
-    rc, so, se = refexec("calculate", src, w, h, dogs, octaves, repr(float(np.float32(1.6))), repr(K_SQRT2), subpixel, out)
+    rc, so, se = refexec("calculate", src, w, h, dogs, octaves, sigma, k, subpixel, out)
     if rc == 5:
         assert so.startswith("EXCEPTION "), so
         return {"exception": so[len("EXCEPTION "):].rstrip("\n") if so.endswith("\n\n") is False else so[len("EXCEPTION "):]}
@@ -116,7 +125,7 @@ def ref_calculate(img, dogs, octaves, subpixel, tmp):
             off += int(lw * lh)
         res[f"{tag}_sha"] = shas
     # the DoG pyramid: Sift::_createDOGs called on its own
-    rc, so, se = refexec("dogs", src, w, h, dogs, octaves, repr(float(np.float32(1.6))), repr(K_SQRT2), subpixel, out)
+    rc, so, se = refexec("dogs", src, w, h, dogs, octaves, sigma, k, subpixel, out)
     assert rc == 0, (rc, so, se)
     dm = np.fromfile(out + ".dogs_meta", np.int64)
     dl = np.fromfile(out + ".dogs", np.float32)
@@ -131,9 +140,12 @@ def ref_calculate(img, dogs, octaves, subpixel, tmp):
 
 def store_calc(store, name, case, tmp):
     """One case of a calculate table: what the reference returned for it, into `store` under calc/<name>/."""
-    spec, dogs, octaves, sub = case
+    spec, dogs, octaves, sub = case[:4]
+    sigma, k = case[4:] if len(case) > 4 else (1.6, K_SQRT2)
     img = make_image(spec)
-    r = ref_calculate(img, dogs, octaves, sub, tmp)
+    r = ref_calculate(img, dogs, octaves, sub, tmp, sigma, k)
+    if len(case) > 4:
+        store[f"calc/{name}/sigma_k"] = np.array([sigma, k], np.float32)
     store[f"calc/{name}/params"] = np.array([dogs, octaves, sub, img.shape[1], img.shape[0]], np.int64)
     store[f"calc/{name}/image_sha"] = np.array(sha(img))
     if "exception" in r:
@@ -213,6 +225,17 @@ def hard_frames():
     print("wrote", HARD_PIN, os.path.getsize(HARD_PIN), "bytes")
 
 
+def scale_steps():
+    assert os.path.exists(REF_BIN), "the reference is not mounted here"
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "_ref/refexec"])
+    store = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for name, case in SCALE_CASES.items():
+            store_calc(store, name, case, tmp)
+    np.savez_compressed(SCALE_PIN, **store)
+    print("wrote", SCALE_PIN, os.path.getsize(SCALE_PIN), "bytes")
+
+
 def long_running(which):
     """The pins that take the reference tens of minutes to hours (it copies three DoG images per candidate and re-blurs a
     level per keypoint); each goes to its own fixture.
@@ -289,6 +312,8 @@ def long_running(which):
 if __name__ == "__main__":
     if sys.argv[1:] == ["hard_frames"]:
         hard_frames()
+    elif sys.argv[1:] == ["scale_steps"]:
+        scale_steps()
     elif len(sys.argv) > 1:
         long_running(sys.argv[1])
     else:

@@ -27,7 +27,13 @@ from sift_amd import _lib                                  # noqa: E402
 from sift_amd.sift import Context                          # noqa: E402
 from sift_amd.synthetic import blob_frame, synth_frame     # noqa: E402
 from hard_frames import GENERATORS                         # noqa: E402
+from oracle_lib import K_SQRT2                             # noqa: E402
 from test_gpu_parity import compare_run                    # noqa: E402
+
+
+# the scale step: the reference's default twice, and steps at which keypoints take their gradient maps from several Gaussian levels
+# (sift.cpp:205-218; tests/test_scale_steps_host.py)
+K_STEPS = [K_SQRT2, K_SQRT2, 1.26, 1.5, 1.7, 2.0]
 
 
 def draw_big(rng):
@@ -36,8 +42,10 @@ def draw_big(rng):
     if rng.random() < 0.5:
         w = w // 4 * 4
     frames = int(rng.choice([1, 2, 3, 4, 6])) if w * h < 3000 * 1000 else int(rng.choice([1, 2]))
-    return dict(w=w, h=h, dogs=int(rng.choice([3, 3, 4])), octaves=int(rng.integers(2, 6)), sigma=float(rng.choice([1.6, 1.6, 1.2])), subpixel=False,
-                frames=frames, streaming=0, blobs=False, seed=int(rng.integers(1, 1 << 20)), hard="")
+    c = dict(w=w, h=h, dogs=int(rng.choice([3, 3, 4])), octaves=int(rng.integers(2, 6)), sigma=float(rng.choice([1.6, 1.6, 1.2])), subpixel=False,
+             frames=frames, streaming=0, blobs=False, seed=int(rng.integers(1, 1 << 20)), hard="")
+    c["k"] = float(rng.choice(K_STEPS))      # drawn last, as in draw()
+    return c
 
 
 def draw(rng):
@@ -63,7 +71,8 @@ def draw(rng):
         hard = str(rng.choice(sorted(GENERATORS)))
         if hard == "mirror4":
             w, h = w // 2 * 2, h // 2 * 2
-    return dict(w=w, h=h, dogs=dogs, octaves=octaves, sigma=sigma, subpixel=subpixel, frames=frames, streaming=streaming, blobs=blobs, seed=seed, hard=hard)
+    k = float(rng.choice(K_STEPS))             # the scale step; drawn last of all, for the same reason
+    return dict(w=w, h=h, dogs=dogs, octaves=octaves, sigma=sigma, subpixel=subpixel, frames=frames, streaming=streaming, blobs=blobs, seed=seed, hard=hard, k=k)
 
 
 def main():
@@ -76,7 +85,7 @@ def main():
     done, failed, skipped = 0, [], 0
     while time.time() < t_end:
         c = draw_big(rng) if big else draw(rng)
-        name = "soak %(w)dx%(h)d dogs %(dogs)d oct %(octaves)d sigma %(sigma)g sub %(subpixel)d x%(frames)d stream %(streaming)d blobs %(blobs)d seed %(seed)d %(hard)s" % c
+        name = "soak %(w)dx%(h)d dogs %(dogs)d oct %(octaves)d sigma %(sigma)g k %(k)g sub %(subpixel)d x%(frames)d stream %(streaming)d blobs %(blobs)d seed %(seed)d %(hard)s" % c
         if c["hard"]:
             img = GENERATORS[c["hard"]](c["w"], c["h"], c["seed"])
         else:
@@ -84,7 +93,7 @@ def main():
         ctx.set_option("stream_min_waves", 1 if c["streaming"] else 0)
         t0 = time.time()
         try:
-            rep = compare_run(ctx, img, c["dogs"], c["octaves"], c["subpixel"], name, report_dir, batch_of=c["frames"], sigma=c["sigma"])
+            rep = compare_run(ctx, img, c["dogs"], c["octaves"], c["subpixel"], name, report_dir, batch_of=c["frames"], sigma=c["sigma"], k=c["k"])
             print("ok   %-110s final %6d  %.1f s" % (name, rep["final"], time.time() - t0), flush=True)
             done += 1
         except AssertionError as e:

@@ -199,9 +199,59 @@ CASES = [
 ]
 
 
+def compare_gradient_maps(ctx, run, image, dogs, octaves, name, rep=None):
+    """The gradient maps of every level: sift_hip_level_copy's `magnitude` / `orientation` against the oracle's.
+
+    The two sides keep a level's maps in different states.  The reference's descriptor stage adds to its maps in place, keypoint
+    after keypoint (sift.cpp:80-92), and the oracle's `level` serves that FINAL state; the library recomputes those additions per
+    keypoint and leaves the maps as the gradient pass wrote them (kernels_desc.hip).  So a map is required bit-identical
+      - to the oracle's final map at every pixel outside the 16x16 windows of the final keypoints that select the level - where
+        final and first state are the same thing (so those windows are all the oracle's map may have changed in) -, and
+      - at every pixel to the oracle's own gradient functions (oracle_gradient: sift.cpp:130-160 for one level) applied to the
+        ORACLE's Gaussian level.
+    Which levels have maps: the reference forms them for every level; the oracle forms a level's when a keypoint first selects it,
+    the library those that the plan's scanned DoG levels select (its restatement of _findNearestGaussian, for any image).  A
+    level the oracle has and the library lacks fails.  A level only the library has - no keypoint of THIS image selects it - is
+    held to the second requirement.  -> (levels both have, levels only the library has)."""
+    import scale_ref
+    final = run.points("final")[0]
+    gauss = [[run.scale("gaussian", o, j) for j in range(dogs + 1)] for o in range(octaves)]
+    nearest = {oi: scale_ref.find_nearest_gaussian(gauss, run.scale("dog", *oi)) for oi in set(zip(final["octave"].tolist(), final["index"].tolist()))}
+    selects = [nearest[oi] for oi in zip(final["octave"].tolist(), final["index"].tolist())]
+    both, library_only = [], []
+    for o in range(octaves):
+        for j in range(dogs + 1):
+            got = {kind: ctx.level(kind, o, j, image) for kind in ("magnitude", "orientation")}
+            want = {kind: run.level(kind, o, j) for kind in ("magnitude", "orientation")}
+            assert (got["magnitude"] is None) == (got["orientation"] is None) and (want["magnitude"] is None) == (want["orientation"] is None)
+            assert want["magnitude"] is None or got["magnitude"] is not None, \
+                f"{name}: level ({o},{j}) img{image}: the oracle has gradient maps (a keypoint selects the level), the library has none"
+            if got["magnitude"] is None:
+                continue
+            (both if want["magnitude"] is not None else library_only).append((o, j))
+            g = run.level("gaussian", o, j)
+            h, w = g.shape
+            first = {"magnitude": np.empty_like(g), "orientation": np.empty_like(g)}
+            O.lib().oracle_gradient(g, w, h, first["magnitude"], first["orientation"])
+            covered = np.zeros((h, w), bool)
+            for x, y, sel in zip(final["x"].tolist(), final["y"].tolist(), selects):
+                if sel == (o, j):
+                    covered[max(y - 8, 0):y + 8, max(x - 8, 0):x + 8] = True
+            for kind in ("magnitude", "orientation"):
+                what = f"{name}: {kind}({o},{j}) img{image}"
+                assert got[kind].shape == (h, w), f"{what}: shape {got[kind].shape} vs oracle {(h, w)}"
+                if want[kind] is not None:
+                    assert_bits_equal(np.where(covered, 0, got[kind]), np.where(covered, 0, want[kind]), what + " outside the keypoints' windows")
+                assert_bits_equal(got[kind], first[kind], what + " against the oracle's gradient of its own level")
+    if rep is not None:
+        rep["gradient_levels"] = [list(l) for l in both]
+        rep["gradient_levels_unselected"] = [list(l) for l in library_only]
+    return both, library_only
+
+
 def compare_image(ctx, run, image, dogs, octaves, subpixel, name, rep):
     """Image `image` of the batch the context holds against one oracle run of that image: the replaced image (subpixel), every
-    Gaussian and DoG level and every stage list; the stage sizes go into `rep`."""
+    Gaussian and DoG level, the gradient maps of every level that has them and every stage list; the stage sizes go into `rep`."""
     if subpixel:
         assert_bits_equal(ctx.image(image), run.image(), f"{name}: replaced image")
     for o in range(octaves):
@@ -211,6 +261,7 @@ def compare_image(ctx, run, image, dogs, octaves, subpixel, name, rep):
         for j in range(dogs):
             assert_bits_equal(ctx.level("dog", o, j, image), run.level("dog", o, j), f"{name}: dog({o},{j}) img{image}")
             assert ctx.level_scale("dog", o, j) == run.scale("dog", o, j)
+    compare_gradient_maps(ctx, run, image, dogs, octaves, name, rep)
     for stage in ("candidates", "after_sort1", "after_orient", "after_sort2", "final"):
         got = ctx.stage(stage, image)
         want, wdesc = run.points(stage)
@@ -226,9 +277,12 @@ def compare_image(ctx, run, image, dogs, octaves, subpixel, name, rep):
             assert_bits_equal(got["orientation"][m], want["orientation"][m], f"{name}: {stage}: orientation")
 
 
-def compare_run(ctx, img, dogs, octaves, subpixel, name, report_dir, batch_of=1, sigma=1.6):
-    params = _lib.Params(dogs, octaves, sigma, O.K_SQRT2, 1 if subpixel else 0)
-    run = O.OracleRun(img, dogs, octaves, sigma=sigma, subpixel=subpixel)
+def compare_run(ctx, img, dogs, octaves, subpixel, name, report_dir, batch_of=1, sigma=1.6, k=O.K_SQRT2, run=None):
+    """`batch_of` copies of `img` in one batch against the oracle's run of it (`run`: that run, where the caller shares one among
+    several tests - it is only read)."""
+    params = _lib.Params(dogs, octaves, sigma, k, 1 if subpixel else 0)
+    if run is None:
+        run = O.OracleRun(img, dogs, octaves, sigma=sigma, k=k, subpixel=subpixel)
     assert run.status == 0, run.error
     imgs = np.stack([img] * batch_of)
     ctx.calculate_batch(imgs, params)
@@ -246,8 +300,8 @@ def compare_run(ctx, img, dogs, octaves, subpixel, name, report_dir, batch_of=1,
         rep["desc_bit_exact"] = bool(d.tobytes() == wdesc.tobytes())
         assert (l2 <= DESC_TOL).all(), f"{name}: descriptors off by up to {l2.max()} (tol {DESC_TOL})"
         assert rep["desc_bit_exact"], f"{name}: descriptors within tolerance but not bit-exact ({int((d != wdesc).sum())} values)"
-        k = kp[image * want.size:(image + 1) * want.size]
-        assert (k["has_descriptor"] == (want["n_desc"] == 128)).all()
+        recs = kp[image * want.size:(image + 1) * want.size]
+        assert (recs["has_descriptor"] == (want["n_desc"] == 128)).all()
     with open(os.path.join(report_dir, "pipeline.jsonl"), "a") as f:
         f.write(json.dumps(rep) + "\n")
     return rep
@@ -595,28 +649,28 @@ def test_batch_images_independent(ctx, report_dir):
         base += counts[i]
 
 
-def test_u8_frames_in_sparse_lists_out(ctx):
-    """The boundary for a host that holds 8-bit frames (the reference's inputs are 8-bit files, main.cpp:52-54): uint8 in
-    (sift_hip_calculate_batch_u8: widened on the GPU to the floats vigra::importImage yields), sparse lists out
-    (sift_hip_result_copy_sparse + sift_hip_sparse_unpack_host) - bit for bit the float path's keypoints and descriptors, from
-    pageable and from page-locked memory, and for a batch without a keypoint."""
+def check_u8_frames_in_sparse_lists_out(ctx, frames, params, min_keypoints):
+    """8-bit frames in, sparse lists out, for the 8-bit valued float frames `frames` under `params`: bit for bit the float path's
+    keypoints and descriptors, from pageable and from page-locked memory; level 1 of every octave of the last frame against the
+    oracle.  -> (counts, keypoint records, descriptors) of the float path."""
     from sift_amd.sift import pinned_array, unpack_sparse_host
-    params = _lib.Params(3, 3, 1.6, O.K_SQRT2, 0)
-    frames = np.stack([synth_frame(333, 257, 70 + i) for i in range(5)])          # odd sizes: the scalar tail of the widening kernel
+    dogs, octaves = params.dogs_per_epoch, params.octaves
     u8 = frames.astype(np.uint8)
     assert np.array_equal(u8.astype(np.float32), frames)                            # the generator's frames are 8-bit valued
     ctx.calculate_batch(frames, params)
     wcounts, (wkp, wdesc) = ctx.counts().copy(), tuple(a.copy() for a in ctx.results())
-    assert wkp.size > 500
+    assert wkp.size > min_keypoints
     pin = pinned_array(u8.shape, np.uint8)
     pin[...] = u8
+    last = len(frames) - 1
+    run = O.OracleRun(frames[last], dogs, octaves, sigma=params.sigma, k=params.k, subpixel=bool(params.subpixel))
     for src in (u8, pin):
         ctx.calculate_batch(src, params)
         assert ctx.counts().tolist() == wcounts.tolist()
         kp, desc = ctx.results()
         assert kp.tobytes() == wkp.tobytes() and desc.tobytes() == wdesc.tobytes()
-        for o in range(3):
-            assert_bits_equal(ctx.level("gaussian", o, 1, 4), O.OracleRun(frames[4], 3, 3).level("gaussian", o, 1), f"g({o},1)")
+        for o in range(octaves):
+            assert_bits_equal(ctx.level("gaussian", o, 1, last), run.level("gaussian", o, 1), f"g({o},1)")
         rec, val = ctx.results_sparse()
         assert rec.shape == (wkp.size, 34) and val.size == int((wdesc.view(np.uint32) != 0).sum())
         for threads in (1, 5):
@@ -625,6 +679,18 @@ def test_u8_frames_in_sparse_lists_out(ctx):
         prec, pval = pinned_array((wkp.size + 7, 34), np.uint8), pinned_array((val.size + 100,), np.float32)
         rec3, val3 = ctx.results_sparse(prec, pval)
         assert rec3.tobytes() == rec.tobytes() and val3.tobytes() == val.tobytes()
+    return wcounts, wkp, wdesc
+
+
+def test_u8_frames_in_sparse_lists_out(ctx):
+    """The boundary for a host that holds 8-bit frames (the reference's inputs are 8-bit files, main.cpp:52-54): uint8 in
+    (sift_hip_calculate_batch_u8: widened on the GPU to the floats vigra::importImage yields), sparse lists out
+    (sift_hip_result_copy_sparse + sift_hip_sparse_unpack_host) - bit for bit the float path's keypoints and descriptors, from
+    pageable and from page-locked memory, and for a batch without a keypoint."""
+    from sift_amd.sift import unpack_sparse_host
+    params = _lib.Params(3, 3, 1.6, O.K_SQRT2, 0)
+    frames = np.stack([synth_frame(333, 257, 70 + i) for i in range(5)])          # odd sizes: the scalar tail of the widening kernel
+    check_u8_frames_in_sparse_lists_out(ctx, frames, params, 500)
     ctx.calculate_batch(np.full((2, 96, 128), 9, np.uint8), params)
     assert ctx.total() == 0
     rec, val = ctx.results_sparse()
@@ -1442,16 +1508,16 @@ def test_batch_pipeline_run_stream(ctx):
         assert got[b][2].tobytes() == kp.tobytes() and got[b][3].tobytes() == desc.tobytes()
 
 
-def test_sparse_wire_kernels_match_the_reference_packing(ctx):
-    """sift_hip_result_sparse_size / _pack (kernels_wire.hip) against the torch restatement of the wire format
-    (sift_amd/gather.py:pack_sparse) on real results, and the round trip back to the 128-float descriptors."""
+def check_sparse_wire_kernels(ctx, frames, params):
+    """sift_hip_result_sparse_size / _pack / sift_hip_sparse_unpack on the results of `frames` under `params` against the torch
+    restatement of the wire format (sift_amd/gather.py:pack_sparse), with the counting pass on its own and (option wire_count)
+    riding in the descriptor kernel.  -> (keypoint records, descriptors)."""
     import torch
     from sift_amd.gather import device_results, join_records, pack_sparse, split_records, unpack_sparse
-    frames = np.stack([synth_frame(640, 480, 30 + i) for i in range(3)] + [np.full((480, 640), 7.0, np.float32)])   # last: no keypoints
-    ctx.calculate_batch(frames, _lib.Params(3, 3, 1.6, O.K_SQRT2, 0))
+    ctx.calculate_batch(frames, params)
     kp, desc = ctx.results()
     total = ctx.total()
-    assert total > 0 and ctx.counts()[-1] == 0
+    assert total > 0
     rec, values = device_results(ctx, total, torch.device("cuda", 0), wire="sparse")
     masks_ref, values_ref = pack_sparse(torch.from_numpy(desc.reshape(-1)))
     rec_ref = join_records(torch.from_numpy(kp.view(np.uint8).reshape(-1)), masks_ref)
@@ -1471,12 +1537,21 @@ def test_sparse_wire_kernels_match_the_reference_packing(ctx):
     # option wire_count: the counting pass rides in the descriptor kernel (what bench.py uses for N > 1); same wire bytes
     ctx.set_option("wire_count", 1)
     try:
-        ctx.calculate_batch(frames, _lib.Params(3, 3, 1.6, O.K_SQRT2, 0))
+        ctx.calculate_batch(frames, params)
         assert ctx.sparse_size() == values_ref.numel()
         rec2, values2 = device_results(ctx, total, torch.device("cuda", 0), wire="sparse")
         assert rec2.cpu().numpy().tobytes() == rec_ref.numpy().tobytes() and values2.cpu().numpy().tobytes() == values_ref.numpy().tobytes()
     finally:
         ctx.set_option("wire_count", 0)
+    return kp, desc
+
+
+def test_sparse_wire_kernels_match_the_reference_packing(ctx):
+    """sift_hip_result_sparse_size / _pack (kernels_wire.hip) against the torch restatement of the wire format
+    (sift_amd/gather.py:pack_sparse) on real results, and the round trip back to the 128-float descriptors."""
+    frames = np.stack([synth_frame(640, 480, 30 + i) for i in range(3)] + [np.full((480, 640), 7.0, np.float32)])   # last: no keypoints
+    check_sparse_wire_kernels(ctx, frames, _lib.Params(3, 3, 1.6, O.K_SQRT2, 0))
+    assert ctx.counts()[-1] == 0
 
 
 def test_deferred_sparse_pack_survives_the_next_batch(ctx):
@@ -1546,10 +1621,11 @@ def test_hip_matches_the_reference_binary_on_hard_frames(ctx, name):
 def hip_against_pin(ctx, pin, cases, name, nan_equals_nan=False):
     import hashlib
     import re
-    spec, dogs, octaves, sub = cases[name]
+    spec, dogs, octaves, sub = cases[name][:4]
+    sigma, k = cases[name][4:] if len(cases[name]) > 4 else (1.6, O.K_SQRT2)      # (REFPIN.SCALE_CASES carry their own)
     img = REFPIN.make_image(spec)
     assert sha(img) == str(pin[f"calc/{name}/image_sha"])
-    params = _lib.Params(dogs, octaves, 1.6, O.K_SQRT2, sub)
+    params = _lib.Params(dogs, octaves, sigma, k, sub)
     if f"calc/{name}/exception" in pin.files:
         with pytest.raises(PreconditionViolation) as e:
             ctx.calculate_batch(img[None], params)

@@ -30,17 +30,22 @@ def vigra_text(msg: str) -> str:
 CALC = sorted(G.CALC_CASES)
 HARD = sorted(G.HARD_CASES)       # tests/hard_frames.py's content, pinned in a fixture of its own
 HARD_PIN = np.load(G.HARD_PIN)
-ALL_CASES = {**G.CALC_CASES, **G.HARD_CASES}
-assert len(ALL_CASES) == len(CALC) + len(HARD)
+SCALE = sorted(G.SCALE_CASES)     # scale steps other than sqrt(2): several gradient levels, pinned in a fixture of their own
+SCALE_PIN = np.load(G.SCALE_PIN)
+ALL_CASES = {**G.CALC_CASES, **G.HARD_CASES, **G.SCALE_CASES}
+assert len(ALL_CASES) == len(CALC) + len(HARD) + len(SCALE)
 
 
-@pytest.mark.parametrize("name", CALC + HARD)
+@pytest.mark.parametrize("name", CALC + HARD + SCALE)
 def test_calculate_matches_the_reference_binary(name):
-    pin = HARD_PIN if name in G.HARD_CASES else PIN
-    spec, dogs, octaves, sub = ALL_CASES[name]
+    pin = HARD_PIN if name in G.HARD_CASES else SCALE_PIN if name in G.SCALE_CASES else PIN
+    spec, dogs, octaves, sub = ALL_CASES[name][:4]
+    sigma, k = ALL_CASES[name][4:] if name in G.SCALE_CASES else (1.6, O.K_SQRT2)
     img = G.make_image(spec)
     assert sha(img) == str(pin[f"calc/{name}/image_sha"]), "input differs from the one the reference saw"
-    run = O.OracleRun(img, dogs, octaves, subpixel=bool(sub))
+    if name in G.SCALE_CASES:
+        assert pin[f"calc/{name}/sigma_k"].tobytes() == np.array([sigma, k], np.float32).tobytes()
+    run = O.OracleRun(img, dogs, octaves, sigma=sigma, k=k, subpixel=bool(sub))
     if f"calc/{name}/exception" in pin.files:
         assert run.status == 1
         assert vigra_text(run.error).strip() == vigra_text(str(pin[f"calc/{name}/exception"])).strip()
@@ -91,6 +96,8 @@ def test_calculate_matches_the_reference_binary(name):
                     assert sha(lv) == str(pin[f"calc/{name}/{key}"][o * mh + j]), f"{kind}({o},{j})"
                     checked += 1
     assert checked >= 2 or ref.size == 0
+    if name in G.SCALE_CASES:                   # maps of three and four levels, octave 0's top level among them
+        assert checked == 2 * {"synth_160x120_5x2_s0.8_k1.5": 4, "synth_200x150_3x3_s1.0_k1.8": 3}[name]
     if f"calc/{name}/desc" in pin.files:        # the small case stored in full
         assert d.tobytes() == pin[f"calc/{name}/desc"].tobytes()
         flat = np.concatenate([run.level("gaussian", o, j).reshape(-1) for o in range(mw) for j in range(mh)])
