@@ -3,7 +3,7 @@
 // or, with model=fundamental, sift::Matcher::verify_fundamental(): a seven-point fundamental matrix, the model for two views of a
 // general scene.  inliers.txt holds the lines of matches.txt that agree with the model.
 //   g++ -std=c++17 -pthread -Iinclude examples/sift_verify.cpp -Lsift_amd/lib -lsift_hip -Wl,-rpath,$PWD/sift_amd/lib -o sift_verify
-//   ./sift_verify a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [refine=0] [model=homography|fundamental]
+//   ./sift_verify a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [refine=0] [model=homography|fundamental] [refit]
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -37,7 +37,7 @@ static void write_matches(const char* path, const std::vector<sift::Match>& matc
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::cerr << "usage: " << argv[0]
-                  << " a.{pgm,ppm,png,jpg} b.{...} [octaves] [dogsPerEpoch] [ratio] [crossCheck] [iterations] [threshold] [seed] [refine] [homography|fundamental]\n";
+                  << " a.{pgm,ppm,png,jpg} b.{...} [octaves] [dogsPerEpoch] [ratio] [crossCheck] [iterations] [threshold] [seed] [refine] [homography|fundamental] [refit]\n";
         return 1;
     }
     const u16_t octaves = argc > 3 ? (u16_t)std::atoi(argv[3]) : 4;
@@ -53,6 +53,12 @@ int main(int argc, char** argv) {
         std::cerr << "model must be homography or fundamental\n";
         return 1;
     }
+    // with model=fundamental: rounds of the least-squares refit of F (sift::Matcher::refine_fundamental), 0 .. 8; absent: no refit
+    const int refit = argc > 12 ? std::atoi(argv[12]) : -1;
+    if (refit >= 0 && model_name != "fundamental") {
+        std::cerr << "refit is for model=fundamental\n";
+        return 1;
+    }
     if (model_name == "fundamental" && refine) {
         std::cerr << "refine is for the homography: there is no least-squares refit of the fundamental matrix\n";
         return 1;
@@ -64,11 +70,14 @@ int main(int argc, char** argv) {
         sift::Matcher matcher;
         const std::vector<sift::Match> matches = matcher.match(a, b, ratio, crossCheck);
         if (model_name == "fundamental") {
-            const sift::Fundamental model = matcher.verify_fundamental(a, b, matches, iterations, threshold, seed, false);
+            sift::Fundamental model = matcher.verify_fundamental(a, b, matches, iterations, threshold, seed, false);
+            int refitted = 0;
+            if (refit >= 0) model = matcher.refine_fundamental(a, b, matches, model, threshold, refit, false, &refitted);
             write_matches("matches.txt", matches, nullptr);
             write_matches("inliers.txt", matches, &model.inlier);
             std::cout << a.size() << " and " << b.size() << " interest points, " << matches.size() << " matches -> matches.txt, " << model.inliers
                       << " inliers -> inliers.txt\n";
+            if (refit >= 0) std::cout << "refitted " << refitted << " rounds\n";
             if (model.iteration < 0) {
                 std::cout << "no fundamental matrix\n";
             } else {

@@ -142,6 +142,35 @@ public:
         return out;
     }
 
+    // The least-squares refit of a fundamental matrix over its own inliers among `matches` (include/sift_hip.h,
+    // sift_hip_refine_fundamental): at most `rounds` rounds, 0 .. 8 (0 only counts), of the normalised eight-point method with a
+    // rank-2 step, from `model` as verify_fundamental() returned it.  The inlier count never decreases; a model that is none
+    // (iteration -1) comes back as it is.  *refined (may be null): the rounds accepted.  Throws std::invalid_argument for rounds
+    // outside 0 .. 8 or a threshold that is not finite and positive.
+    Fundamental refine_fundamental(const std::vector<InterestPoint>& query, const std::vector<InterestPoint>& train, const std::vector<Match>& matches,
+                                   const Fundamental& model, f32_t threshold = 3.0f, int rounds = 2, bool subpixel = false, int* refined = nullptr) {
+        gather(query, train, matches, subpixel);
+        const int64_t offsets[2] = {0, (int64_t)matches.size()};
+        sift_hip_fundamental rec{};
+        for (int k = 0; k < 9; ++k) rec.f[k] = model.f[k];
+        rec.inliers = model.inliers;
+        rec.iteration = model.iteration;
+        rec.root = model.root;
+        Fundamental out;
+        out.inlier.assign(matches.size(), 0);
+        int32_t accepted = 0;
+        char err[512] = "";
+        const int rc = sift_hip_refine_fundamental(_ctx, _pts.data(), 1, offsets, threshold, rounds, &rec, &accepted, out.inlier.data(), err, sizeof(err));
+        if (rc == SIFT_HIP_EINVAL) throw std::invalid_argument(err);
+        if (rc != SIFT_HIP_OK) throw std::runtime_error(err);
+        for (int k = 0; k < 9; ++k) out.f[k] = rec.f[k];
+        out.inliers = rec.inliers;
+        out.iteration = rec.iteration;
+        out.root = rec.root;
+        if (refined) *refined = accepted;
+        return out;
+    }
+
 private:
     // both lists' descriptor rows and valid flags -> _desc, _kp
     void rows(const std::vector<InterestPoint>& query, const std::vector<InterestPoint>& train) {

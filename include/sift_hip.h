@@ -343,8 +343,8 @@ int sift_hip_result_verify(sift_hip_ctx* ctx, int n_pairs, const int32_t* pair_q
  *              slot among equals.  No valid slot, or m < 7: iteration -1, root -1, inliers 0, f all +0.0f, every flag 0.
  * Scores are integers, so the result does not depend on tiling, splits or reduction order.  Caveats: with exactly seven rows
  * every sample is the same seven rows; a planar scene or a pure rotation does not determine F (sift_hip_ransac_homography is
- * the right call there); there is no oriented-epipolar test.  A least-squares refit of F is out of scope: params->refine must
- * be 0. */
+ * the right call there); there is no oriented-epipolar test.  params->refine must be 0 here: the least-squares refit of F is a call
+ * of its own, sift_hip_refine_fundamental below. */
 typedef struct sift_hip_fundamental {
     float f[9];           /* row-major */
     int32_t inliers;      /* inliers of f = number of flags set = the score of the winner */
@@ -363,6 +363,36 @@ int sift_hip_result_verify_fundamental(sift_hip_ctx* ctx, int n_pairs, const int
                                        const sift_hip_match_params* match_params, const sift_hip_ransac_params* ransac_params,
                                        sift_hip_match_rec* recs, int32_t* counts, int64_t* total, sift_hip_fundamental* models,
                                        uint8_t* inlier, char* err, int errlen);
+/* The least-squares refit of F from its own inliers (an extension), the sibling of sift_hip_refine_homography: no sampling,
+ * models in and out.  sift_amd/csrc/ransac_fund_refine_math.h defines a round bit for bit; the host loop is
+ * hostmath_refine_fundamental.  A round from the model f with the score c = its inliers: n = the inliers of f under the
+ * predicate above; the centroids and power-of-two scales of the homography refit's normalisation; with x, y the normalised
+ * query and u, v the normalised train coordinates, the 35 fixed-order sums of P Q, P in {1, u, v, uu, uv, vv}, Q in {1, x, y,
+ * xx, xy, yy}, which are the 9 x 9 matrix S = sum a a^T of the rows a = [ux uy u vx vy v x y 1]; the entry e of largest
+ * magnitude of f in normalised coordinates is fixed to 1 and the other eight come from S[-e,-e] g = -S[-e,e] by the homography
+ * refit's elimination; rank 2 without SVD or square root (the lowest root of the characteristic cubic of F^T F by bracketed
+ * bisection, its null vector v by a cross product, F - (F v) v^T / (v . v)); denormalisation, division by the first entry of
+ * largest magnitude (which becomes +1), nine floats; c' = the inliers of the new model among all rows.  The round fails - f
+ * stays, the rounds end - when n < 8, a side's spread is zero or not finite, a pivot is zero or not finite, the cubic has no
+ * bracketed root, v . v is zero or not finite, or an entry is not finite.  The new model is accepted when c' >= c and another
+ * round follows only when c' > c: the inlier count never decreases.  The error minimised is algebraic and unweighted: there is
+ * no Sampson-weighted or iterative (Levenberg-Marquardt) refinement and no oriented-epipolar test.
+ * models: n_sets records, in and out.  A model with iteration >= 0 runs at most `rounds` rounds (0 .. 8; 0 only counts) and
+ * gets f and inliers (the count under the final f) rewritten; iteration and root stay as given.  A model with iteration < 0 is
+ * left alone and all its flags are 0.  refined (may be NULL): one int32 per set, the rounds accepted.  pts, offsets, inlier and
+ * the memory rules as for sift_hip_ransac_homography; models and refined may each be host or device memory.  One launch for
+ * all sets.  SIFT_HIP_EINVAL for rounds outside 0 .. 8, a threshold that is not finite and positive, or bad offsets. */
+int sift_hip_refine_fundamental(sift_hip_ctx* ctx, const float* pts, int n_sets, const int64_t* offsets, float threshold,
+                                int rounds, sift_hip_fundamental* models, int32_t* refined, uint8_t* inlier, char* err, int errlen);
+/* The refit over the device-resident batch, after sift_hip_result_verify_fundamental: pair_q, pair_t, recs, counts and models
+ * as that call took and delivered them (recs and models host or device memory; counts host).  The coordinates are built on the
+ * GPU as for sift_hip_result_verify; bit for bit sift_hip_refine_fundamental on those coordinates, pair p being set p.  Only
+ * models, refined and flags leave the GPU, but for records in device memory, which are read back once: every record's indices
+ * are checked against the batch (SIFT_HIP_EINVAL) before a kernel reads keypoints by them.  inlier (may be NULL): one byte per
+ * record. */
+int sift_hip_result_refine_fundamental(sift_hip_ctx* ctx, int n_pairs, const int32_t* pair_q, const int32_t* pair_t,
+                                       const sift_hip_match_rec* recs, const int32_t* counts, float threshold, int rounds,
+                                       sift_hip_fundamental* models, int32_t* refined, uint8_t* inlier, char* err, int errlen);
 
 /* ---- guided matching: descriptor matching under a verified model (an extension) ----------------------------
  * Everything of "descriptor matching" above holds unchanged - the fmaf chain, d2, the order (d2, index), validity, sets, pairs

@@ -38,6 +38,7 @@ SYMBOLS = [
     "sift_hip_knn2", "sift_hip_match", "sift_hip_result_match",
     "sift_hip_ransac_homography", "sift_hip_result_verify", "sift_hip_refine_homography",
     "sift_hip_ransac_fundamental", "sift_hip_result_verify_fundamental",
+    "sift_hip_refine_fundamental", "sift_hip_result_refine_fundamental",
     "sift_hip_knn2_guided", "sift_hip_match_guided", "sift_hip_result_match_guided",
     "sift_hip_quantize", "sift_hip_result_copy_u8", "sift_hip_knn2_u8", "sift_hip_match_u8",
 ]
@@ -209,6 +210,8 @@ def load():
                                          vp, vp, cs, ci]
     L.sift_hip_ransac_fundamental.argtypes = L.sift_hip_ransac_homography.argtypes
     L.sift_hip_result_verify_fundamental.argtypes = L.sift_hip_result_verify.argtypes
+    L.sift_hip_refine_fundamental.argtypes = [vp, vp, ci, i64p, C.c_float, ci, vp, vp, vp, cs, ci]
+    L.sift_hip_result_refine_fundamental.argtypes = [vp, ci, i32p, i32p, vp, i32p, C.c_float, ci, vp, vp, vp, cs, ci]
     # xy and models may be host or device memory as well
     gp = C.POINTER(GuideParams)
     L.sift_hip_knn2_guided.argtypes = [vp, vp, vp, vp, ci, i64p, ci, i32p, i32p, gp, vp, vp, vp, cs, ci]

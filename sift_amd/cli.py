@@ -4,7 +4,7 @@ overlay :59-76) on top of the GPU path — SURVEY.md §8(f) rows 1-3.
     python -m sift_amd.cli -i image.pgm [-s 1.6] [-k 1.41421354] [-o 4] [-d 3] [-p 0] [-r 1]
     python -m sift_amd.cli -i a.pgm --match b.pgm [--ratio 0.8] [--cross-check]      (an extension: matches.txt)
     python -m sift_amd.cli -i a.pgm --match b.pgm --u8 [--verify ...]                (8-bit descriptors, integer distances)
-    python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--iterations 2048] [--threshold 3] [--seed 0] [--refine 0] [--model homography|fundamental]   (... and inliers.txt)
+    python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--iterations 2048] [--threshold 3] [--seed 0] [--refine 0] [--model homography|fundamental] [--refit N]   (... and inliers.txt)
     python -m sift_amd.cli -i a.pgm --match b.pgm --verify --guided [--guided-ratio R]   (... and guided.txt: the matches again, under the verified model)
 
 Image ingest follows Vigra's scalar import: band 0 of multi-band files, values unscaled.  PGM,
@@ -142,6 +142,8 @@ def main(argv=None) -> int:
     ap.add_argument("--model", choices=("homography", "fundamental"), default="homography",
                     help="model of --verify: a four-point homography (a plane or a rotating camera), or a seven-point fundamental matrix "
                          "(two views of a general scene)")
+    ap.add_argument("--refit", type=int, default=None, metavar="N",
+                    help="with --verify --model fundamental: at most N rounds (0 .. 8) of the least-squares refit of F over its inliers")
     ap.add_argument("--guided", action="store_true",
                     help="with --verify: match again under the winning model (a point competes only within --threshold pixels of it); "
                          "the matches go to guided.txt")
@@ -168,6 +170,10 @@ def main(argv=None) -> int:
         ap.error("--refine needs --verify")
     if not 0 <= args.refine <= 8:
         ap.error("--refine must be 0 .. 8")
+    if args.refit is not None and not (args.verify and args.model == "fundamental"):
+        ap.error("--refit needs --verify --model fundamental")
+    if args.refit is not None and not 0 <= args.refit <= 8:
+        ap.error("--refit must be 0 .. 8")
     path = args.img or args.img_pos
     if not path:
         ap.print_help()
@@ -188,6 +194,8 @@ def main(argv=None) -> int:
             else:
                 matches, model, inlier = sift.verify(points, points2, args.ratio, args.cross_check, args.iterations, args.threshold, args.seed,
                                                      args.refine, args.model, args.u8)
+                if args.refit is not None:
+                    model, refitted, inlier = sift.refine_fundamental(points, points2, matches, model, args.threshold, args.refit)
             write_matches("matches.txt", matches)
             print(f"{len(points2)} interest points in {args.match}, {len(matches)} matches")
             if args.verify:
@@ -195,6 +203,8 @@ def main(argv=None) -> int:
                 print(f"{int(model['inliers'])} inliers -> inliers.txt")
                 if args.refine:
                     print(f"refined {int(model['refined'])} rounds")
+                if args.refit is not None:
+                    print(f"refitted {refitted} rounds")
                 if args.model == "fundamental":
                     if model["iteration"] < 0:
                         print("no fundamental matrix")

@@ -11,6 +11,7 @@
 #include "ransac_fund_math.h"
 #include "ransac_math.h"
 #include "ransac_refine_math.h"
+#include "ransac_fund_refine_math.h"
 #include "../../include/sift_hip.h"   // sift_hip_homography, sift_hip_fundamental
 
 extern "C" {
@@ -446,5 +447,105 @@ void hostmath_ransac_fundamental(const float* pts, int n_sets, const int64_t* of
                 inlier[offsets[s] + i] =
                     best.iteration >= 0 && sift_hip::ransac_fund_inlier(best.f, p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], thr2) ? 1 : 0;
     }
+}
+}
+
+// ---- the refit of F as ransac_fund_refine_math.h defines it, in plain loops: what ransac_fund_refine_kernel must reproduce
+// bit for bit.
+namespace {
+int fund_refine_count(const float* p, int64_t m, const float (&f)[9], float thr2) {
+    int c = 0;
+    for (int64_t i = 0; i < m; ++i) c += ransac_fund_inlier(f, p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], thr2) ? 1 : 0;
+    return c;
+}
+// K fixed-order sums over the inliers of f (refine_fixed_sums with the epipolar predicate)
+template <int K, typename Terms>
+int fund_refine_fixed_sums(const float* p, int64_t m, const float (&f)[9], float thr2, Terms terms, double (&out)[K]) {
+    double s[K][kRefineLanes];
+    for (int k = 0; k < K; ++k)
+        for (int l = 0; l < kRefineLanes; ++l) s[k][l] = 0.0;
+    int n = 0;
+    for (int64_t i = 0; i < m; ++i) {
+        if (!ransac_fund_inlier(f, p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], thr2)) continue;
+        double t[K];
+        terms(p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], t);
+        for (int k = 0; k < K; ++k) s[k][i % kRefineLanes] = s[k][i % kRefineLanes] + t[k];
+        ++n;
+    }
+    for (int k = 0; k < K; ++k) out[k] = refine_tree256(s[k]);
+    return n;
+}
+// the first two passes of a round: n, the normalisation and the 36 sums (S36[0] = n); false when the round fails there
+bool fund_refine_sums36(const float* p, int64_t m, const float (&f)[9], float thr2, int& n, RefineNorm& nm, double (&S36)[36]) {
+    double mom[kRefineMoments], s[kFundRefineSums];
+    n = fund_refine_fixed_sums<kRefineMoments>(
+        p, m, f, thr2, [](float a, float b, float c, float d, double (&t)[kRefineMoments]) { refine_moment_terms(a, b, c, d, t); }, mom);
+    if (n < kFundRefineMinRows || !refine_normalisation(mom, n, nm)) return false;
+    fund_refine_fixed_sums<kFundRefineSums>(
+        p, m, f, thr2, [&nm](float a, float b, float c, float d, double (&t)[kFundRefineSums]) { fund_refine_terms(nm, a, b, c, d, t); }, s);
+    S36[0] = (double)n;
+    for (int k = 0; k < kFundRefineSums; ++k) S36[k + 1] = s[k];
+    return true;
+}
+// one round: f -> f2; false when the round fails
+bool fund_refine_round(const float* p, int64_t m, const float (&f)[9], float thr2, float (&f2)[9]) {
+    double S36[36], M[72], g[8];
+    RefineNorm nm;
+    int n;
+    if (!fund_refine_sums36(p, m, f, thr2, n, nm, S36)) return false;
+    const int e = fund_refine_gauge(f, nm);
+    for (int r = 0; r < 8; ++r)
+        for (int c = 0; c < 9; ++c) M[9 * r + c] = fund_refine_system_entry(S36, e, r, c);
+    if (!refine_solve8(M, g)) return false;
+    for (int k = 0; k < 9; ++k) f2[k] = f[k];
+    return fund_refine_finish(g, e, nm, f2);
+}
+}  // namespace
+
+extern "C" {
+// models: in-out; rounds 0 .. 8 (0 only counts the inliers of the given models); refined (may be NULL): the rounds accepted
+void hostmath_refine_fundamental(const float* pts, int n_sets, const int64_t* offsets, float thr, int rounds, sift_hip_fundamental* models,
+                                 int32_t* refined, uint8_t* inlier) {
+    const float thr2 = thr * thr;
+    if (inlier && n_sets > 0)
+        for (int64_t i = 0; i < offsets[0]; ++i) inlier[i] = 0;
+    for (int s = 0; s < n_sets; ++s) {
+        const float* p = pts + 4 * offsets[s];
+        const int64_t m = offsets[s + 1] - offsets[s];
+        sift_hip_fundamental& mdl = models[s];
+        int accepted = 0;
+        if (mdl.iteration >= 0) {   // a model that is none is left alone
+            int c = fund_refine_count(p, m, mdl.f, thr2);
+            for (int r = 0; r < rounds; ++r) {
+                float f2[9];
+                if (!fund_refine_round(p, m, mdl.f, thr2, f2)) break;
+                const int c2 = fund_refine_count(p, m, f2, thr2);
+                if (c2 < c) break;
+                for (int k = 0; k < 9; ++k) mdl.f[k] = f2[k];
+                ++accepted;
+                if (c2 == c) break;
+                c = c2;
+            }
+            mdl.inliers = c;
+        }
+        if (refined) refined[s] = accepted;
+        if (inlier)
+            for (int64_t i = 0; i < m; ++i)
+                inlier[offsets[s] + i] =
+                    mdl.iteration >= 0 && ransac_fund_inlier(mdl.f, p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], thr2) ? 1 : 0;
+    }
+}
+// The sums of one round over m rows under f: out[0] = n, out[1 .. 35] the 35 fixed-order sums (P-major: 6 a + b holds P[a] Q[b]);
+// norm[0 .. 5] = cqx, cqy, sq, ctx, cty, st.  Returns n, or -1 - n when n < 8 or the normalisation fails (out is then untouched).
+int hostmath_fund_refine_sums(const float* pts, long long m, const float* f, float thr, double* out, double* norm) {
+    float ff[9];
+    for (int k = 0; k < 9; ++k) ff[k] = f[k];
+    double S36[36];
+    RefineNorm nm;
+    int n;
+    if (!fund_refine_sums36(pts, m, ff, thr * thr, n, nm, S36)) return -1 - n;
+    for (int k = 0; k < 36; ++k) out[k] = S36[k];
+    norm[0] = nm.cqx; norm[1] = nm.cqy; norm[2] = nm.sq; norm[3] = nm.ctx; norm[4] = nm.cty; norm[5] = nm.st;
+    return n;
 }
 }

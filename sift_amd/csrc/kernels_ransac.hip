@@ -10,6 +10,7 @@
 // short lists (a few hundred rows) that a ratio test leaves; this one wastes lanes only below 256 iterations.
 #include "ransac_kernels.h"
 #include "ransac_fund_math.h"
+#include "ransac_fund_refine_math.h"
 #include "ransac_math.h"
 #include "ransac_refine_math.h"
 
@@ -319,6 +320,160 @@ __global__ __launch_bounds__(kRefineLanes) void ransac_refine_kernel(const float
     }
 }
 
+// The refit of F (ransac_fund_refine_math.h): one workgroup of kRefineLanes lanes per set, every round of the set in this one
+// launch, every decision computed by every lane from the same LDS values - the frame of ransac_refine_kernel.  Its own:
+//   rows    a round walks the set three times and there are up to eight rounds, so a set of m <= stage_rows (at most
+//           kFundRefineRows) rows is copied to LDS once, as 16-byte rows; lane p reads rows p, p + 256, .. - consecutive
+//           ds_read_b128, no bank conflict.  A longer set is read from global memory every time.  The rows are the same floats
+//           either way, so the result is the same bits.
+//   mask    the lane keeps the predicate's outcome of its first 64 rows of pass 1 in a 64-bit mask (16 384 rows a set) and
+//           pass 2 reads the bit; beyond that it evaluates the predicate again, which gives the same outcome.  Iteration k
+//           of a lane's loop is the same k in every lane, so the choice between bit and predicate is uniform.
+//   sums    the 35 fixed-order sums are 35 double accumulators a lane (70 VGPRs): the butterfly inside the wave, the four
+//           waves' sums through LDS as (W0 + W1) + (W2 + W3), the 36 values in LDS (s_S[0] = n).
+//   solve   lane 9 i + j builds and updates entry (i, j) of the 8 x 9 system in LDS; the gauge, the back-substitution, the
+//           rank-2 step and the denormalisation run in every lane from those shared values: straight-line selects, no scratch.
+__global__ __launch_bounds__(kRefineLanes) void ransac_fund_refine_kernel(const float* __restrict__ pts, const int64_t* __restrict__ off, int rounds,
+                                                                          float thr2, int stage_rows, sift_hip_fundamental* __restrict__ models,
+                                                                          int32_t* __restrict__ refined_out) {
+    __shared__ __attribute__((aligned(16))) f4v s_rows[kFundRefineRows];
+    __shared__ double s_part[kFundRefineSums * 4];   // the waves' sums of a pass
+    __shared__ double s_S[36];                       // n and the 35 sums
+    __shared__ double s_M[72];                       // the augmented system
+    __shared__ int s_cnt[4];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    sift_hip_fundamental* mdl = models + blockIdx.x;
+    if (mdl->iteration < 0) {   // none: left alone.  The whole workgroup, before any barrier.
+        if (tid == 0 && refined_out) refined_out[blockIdx.x] = 0;
+        return;
+    }
+    const int64_t row0 = off[blockIdx.x];
+    const int m = (int)(off[blockIdx.x + 1] - row0);
+    const f4v* __restrict__ g_rows = reinterpret_cast<const f4v*>(pts + 4 * row0);
+    const bool staged = m <= stage_rows;   // stage_rows <= kFundRefineRows (the launcher clamps it)
+    if (staged)
+        for (int i = tid; i < m; i += kRefineLanes) s_rows[i] = g_rows[i];
+    const auto row = [&](int i) -> f4v { return staged ? s_rows[i] : g_rows[i]; };
+    float f[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) f[k] = mdl->f[k];
+    int c = 0, refined = 0;
+    for (int round = 0; round < (rounds > 0 ? rounds : 1); ++round) {
+        __syncthreads();   // the staged rows are written; the LDS of the previous round is read
+        // ---- pass 1: the inliers of f, their mask and their moments ----
+        int n = 0;
+        uint64_t mask = 0;
+        double mom[kRefineMoments];
+#pragma unroll
+        for (int k = 0; k < kRefineMoments; ++k) mom[k] = 0.0;
+        for (int i = tid, k = 0; i < m; i += kRefineLanes, ++k) {
+            const f4v r = row(i);
+            const bool in = ransac_fund_inlier(f, r.x, r.y, r.z, r.w, thr2);
+            double t[kRefineMoments];
+            refine_moment_terms(r.x, r.y, r.z, r.w, t);
+            n += in ? 1 : 0;
+            mask |= (k < 64 && in) ? (uint64_t)1 << (k & 63) : (uint64_t)0;
+#pragma unroll
+            for (int j = 0; j < kRefineMoments; ++j) mom[j] = in ? mom[j] + t[j] : mom[j];
+        }
+        n = refine_wave_count(n);
+#pragma unroll
+        for (int k = 0; k < kRefineMoments; ++k) mom[k] = refine_wave_sum(mom[k]);
+        if ((tid & 63) == 0) {
+            s_cnt[wave] = n;
+#pragma unroll
+            for (int k = 0; k < kRefineMoments; ++k) s_part[4 * k + wave] = mom[k];
+        }
+        __syncthreads();
+        n = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+#pragma unroll
+        for (int k = 0; k < kRefineMoments; ++k) mom[k] = (s_part[4 * k] + s_part[4 * k + 1]) + (s_part[4 * k + 2] + s_part[4 * k + 3]);
+        c = n;   // the score of f is its inlier count
+        if (rounds == 0) break;
+        RefineNorm nm;
+        if (n < kFundRefineMinRows || !refine_normalisation(mom, n, nm)) break;
+        __syncthreads();   // s_part is read
+        // ---- pass 2: the 35 moment sums ----
+        {
+            double acc[kFundRefineSums];
+#pragma unroll
+            for (int k = 0; k < kFundRefineSums; ++k) acc[k] = 0.0;
+            for (int i = tid, k = 0; i < m; i += kRefineLanes, ++k) {
+                const f4v r = row(i);
+                bool in;
+                if (k < 64) in = ((mask >> k) & 1u) != 0;
+                else in = ransac_fund_inlier(f, r.x, r.y, r.z, r.w, thr2);
+                double t[kFundRefineSums];
+                fund_refine_terms(nm, r.x, r.y, r.z, r.w, t);
+#pragma unroll
+                for (int j = 0; j < kFundRefineSums; ++j) acc[j] = in ? acc[j] + t[j] : acc[j];
+            }
+#pragma unroll
+            for (int k = 0; k < kFundRefineSums; ++k) acc[k] = refine_wave_sum(acc[k]);
+            if ((tid & 63) == 0) {
+#pragma unroll
+                for (int k = 0; k < kFundRefineSums; ++k) s_part[4 * k + wave] = acc[k];
+            }
+            __syncthreads();
+            if (tid < kFundRefineSums) s_S[tid + 1] = (s_part[4 * tid] + s_part[4 * tid + 1]) + (s_part[4 * tid + 2] + s_part[4 * tid + 3]);
+            if (tid == kFundRefineSums) s_S[0] = (double)n;
+            __syncthreads();
+        }
+        // ---- the system: the gauge in every lane, entry (i, j) by lane 9 i + j ----
+        const int e = fund_refine_gauge(f, nm);
+        const int ei = tid / 9, ej = tid - 9 * ei;   // this lane's entry, for tid < 72
+        if (tid < 72) s_M[tid] = fund_refine_system_entry(s_S, e, ei, ej);
+        __syncthreads();
+        // ---- the solve: step k reads its inputs, a barrier, writes, a barrier ----
+        bool ok = true;
+        for (int k = 0; k < 8; ++k) {
+            bool piv_ok;
+            const int p = refine_pivot(s_M, k, piv_ok);
+            ok &= piv_ok;
+            double val = 0.0, pj = 0.0, fac = 0.0;
+            const bool mine = tid < 72 && ei >= k;
+            if (mine) {
+                const int src = ei == k ? p : (ei == p ? k : ei);   // rows k and p change places
+                val = s_M[9 * src + ej];
+                pj = s_M[9 * p + ej];
+                fac = s_M[9 * src + k] / s_M[9 * p + k];
+            }
+            __syncthreads();
+            if (mine) s_M[9 * ei + ej] = (ei > k && ej > k) ? refine_eliminate(fac, pj, val) : val;
+            __syncthreads();
+        }
+        double g[8];
+        ok &= refine_backsubstitute(s_M, g);
+        float f2[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) f2[k] = f[k];
+        ok = ok && fund_refine_finish(g, e, nm, f2);
+        if (!ok) break;
+        // ---- pass 3: the score of the new model ----
+        int c2 = 0;
+        for (int i = tid; i < m; i += kRefineLanes) {
+            const f4v r = row(i);
+            c2 += ransac_fund_inlier(f2, r.x, r.y, r.z, r.w, thr2) ? 1 : 0;
+        }
+        c2 = refine_wave_count(c2);
+        if ((tid & 63) == 0) s_cnt[wave] = c2;
+        __syncthreads();
+        c2 = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+        if (c2 < c) break;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) f[k] = f2[k];
+        ++refined;
+        c = c2;
+        if (c2 == n) break;
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) mdl->f[k] = f[k];
+        mdl->inliers = c;
+        if (refined_out) refined_out[blockIdx.x] = refined;
+    }
+}
+
 // one lane per row: the predicate under the winner of the row's set
 template <typename Model>
 __global__ __launch_bounds__(256) void ransac_flags_kernel(const float* __restrict__ pts, const int64_t* __restrict__ off, int n_sets, long long rows,
@@ -399,6 +554,12 @@ void launch_fund_flags(hipStream_t s, const float* d_pts, const int64_t* d_off, 
     if (rows <= 0 || n_sets <= 0) return;
     hipLaunchKernelGGL(ransac_flags_kernel<FundamentalModel>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, d_pts, d_off, n_sets, rows, d_models, thr2,
                        d_inlier);
+}
+void launch_fund_refine(hipStream_t s, const float* d_pts, const int64_t* d_off, int n_sets, int rounds, float thr2, int stage_rows,
+                        sift_hip_fundamental* d_models, int32_t* d_refined) {
+    if (n_sets <= 0) return;
+    const int cap = stage_rows < 0 ? 0 : (stage_rows > kFundRefineRows ? kFundRefineRows : stage_rows);
+    hipLaunchKernelGGL(ransac_fund_refine_kernel, dim3((unsigned)n_sets), dim3(kRefineLanes), 0, s, d_pts, d_off, rounds, thr2, cap, d_models, d_refined);
 }
 void launch_ransac_gather(hipStream_t s, const sift_hip_match_rec* d_recs, const int64_t* d_off, int n_pairs, long long rows,
                           const sift_hip_keypoint* d_kp, const int* d_kp_row0, float coord_scale, float* d_pts) {

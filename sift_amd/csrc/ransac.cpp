@@ -17,13 +17,15 @@ struct RansacState {
     ScratchBuf d_off, d_tiles, d_kp_row0;    // the tables
     ScratchBuf d_hyp, d_scores;              // every hypothesis' model and score
     ScratchBuf d_models, d_inlier;           // results on their way to host memory
+    ScratchBuf d_refined;                    // sift_hip_refine_fundamental: the rounds accepted, likewise
+    ScratchBuf d_recs;                       // sift_hip_result_refine_fundamental: records that arrive in host memory
     void* h_tables = nullptr;                // page-locked image of the tables (the copies are asynchronous)
     size_t h_cap = 0;
 };
 
 void ransac_state_free(RansacState* st) {
     if (!st) return;
-    for (ScratchBuf* b : {&st->d_pts, &st->d_off, &st->d_tiles, &st->d_kp_row0, &st->d_hyp, &st->d_scores, &st->d_models, &st->d_inlier}) b->release();
+    for (ScratchBuf* b : {&st->d_pts, &st->d_off, &st->d_tiles, &st->d_kp_row0, &st->d_hyp, &st->d_scores, &st->d_models, &st->d_inlier, &st->d_refined, &st->d_recs}) b->release();
     if (st->h_tables) {
         ApiGuard api;
         (void)hipHostFree(st->h_tables);
@@ -71,7 +73,10 @@ struct Job {
     bool refine_only = false;   // sift_hip_refine_homography: `models` are the caller's, no sampling; params is null
     float threshold = 0.0f;     //   its threshold and rounds
     int rounds = 0;
-    bool fund = false;          // the fundamental matrix: seven-point samples, three hypothesis slots per sample, no refinement
+    bool fund = false;          // the fundamental matrix: seven-point samples, three hypothesis slots per sample; with
+                                //   refine_only, sift_hip_refine_fundamental: the refit of the caller's models
+    int32_t* refined = nullptr; //   its rounds accepted per set (may be null; host or device memory)
+    const sift_hip_match_rec* h_recs = nullptr;   // records in host memory that `gather` needs on the device (its d_recs is null)
 };
 
 int run(void* arg) {
@@ -127,6 +132,16 @@ int run(void* arg) {
 
     // ---- rows on the device ----
     const float* d_pts = j.pts;
+    Gather gather_dev{};
+    if (j.gather) {
+        gather_dev = *j.gather;
+        if (!gather_dev.d_recs && rows > 0) {
+            st.d_recs.ensure((size_t)rows * sizeof(sift_hip_match_rec));
+            match_upload(j.c, st.d_recs.p, j.h_recs, (size_t)rows * sizeof(sift_hip_match_rec));
+            match_wait(j.c);
+            gather_dev.d_recs = st.d_recs.as<sift_hip_match_rec>();
+        }
+    }
     if (j.gather || (rows > 0 && !match_ptr_on_device(j.pts))) {
         st.d_pts.ensure((size_t)std::max<long long>(rows, 1) * 4 * sizeof(float));
         if (!j.gather) {
@@ -174,11 +189,14 @@ int run(void* arg) {
     sift_hip_homography* d_hmodels = static_cast<sift_hip_homography*>(d_models);
     sift_hip_fundamental* d_fmodels = static_cast<sift_hip_fundamental*>(d_models);
     uint8_t* d_inlier = inlier_direct ? j.inlier : st.d_inlier.as<uint8_t>();
+    const bool refined_direct = j.refined && match_ptr_on_device(j.refined);
+    if (j.refined && !refined_direct) st.d_refined.ensure((size_t)j.n_sets * sizeof(int32_t));
+    int32_t* d_refined = !j.refined ? nullptr : (refined_direct ? j.refined : st.d_refined.as<int32_t>());
 
     // ---- the launches: one of each kernel, whatever the number of sets ----
     if (j.gather)
-        launch_ransac_gather(v.stream, j.gather->d_recs, st.d_off.as<int64_t>(), j.n_sets, rows, j.gather->d_kp, st.d_kp_row0.as<int>(),
-                             j.gather->coord_scale, st.d_pts.as<float>());
+        launch_ransac_gather(v.stream, gather_dev.d_recs, st.d_off.as<int64_t>(), j.n_sets, rows, gather_dev.d_kp, st.d_kp_row0.as<int>(),
+                             gather_dev.coord_scale, st.d_pts.as<float>());
     if (j.refine_only) {
         if (!models_direct) {
             match_upload(j.c, d_models, j.models, (size_t)j.n_sets * sizeof(sift_hip_homography));
@@ -196,13 +214,15 @@ int run(void* arg) {
         launch_ransac_select(v.stream, st.d_hyp.as<RansacHyp>(), j.n_sets, iters, d_scores, d_hmodels);
     }
     // every round of every set in one launch; with refine 0 the models are the selection's
-    if (j.refine_only || rounds > 0) launch_ransac_refine(v.stream, d_pts, st.d_off.as<int64_t>(), j.n_sets, rounds, thr2, d_hmodels);
+    if (j.refine_only && j.fund) launch_fund_refine(v.stream, d_pts, st.d_off.as<int64_t>(), j.n_sets, rounds, thr2, kFundRefineRows, d_fmodels, d_refined);
+    else if (j.refine_only || rounds > 0) launch_ransac_refine(v.stream, d_pts, st.d_off.as<int64_t>(), j.n_sets, rounds, thr2, d_hmodels);
     if (j.inlier && j.fund) launch_fund_flags(v.stream, d_pts, st.d_off.as<int64_t>(), j.n_sets, rows, d_fmodels, thr2, d_inlier);
     if (j.inlier && !j.fund) launch_ransac_flags(v.stream, d_pts, st.d_off.as<int64_t>(), j.n_sets, rows, d_hmodels, thr2, d_inlier);
     SIFT_HIP_CHECK(hipGetLastError());
 
     if (!models_direct) match_download(j.c, j.models, d_models, (size_t)j.n_sets * sizeof(sift_hip_homography));
     if (j.inlier && !inlier_direct) match_download(j.c, j.inlier, d_inlier, (size_t)rows);
+    if (j.refined && !refined_direct) match_download(j.c, j.refined, d_refined, (size_t)j.n_sets * sizeof(int32_t));
     if (j.scores && !scores_direct) match_download(j.c, j.scores, d_scores, (size_t)n_hyp * sizeof(int32_t));
     match_wait(j.c);
     return SIFT_HIP_OK;
@@ -229,6 +249,76 @@ int sift_hip_refine_homography(sift_hip_ctx* c, const float* pts, int n_sets, co
     j.refine_only = true;
     j.threshold = threshold;
     j.rounds = rounds;
+    return match_guarded(err, errlen, run, &j);
+}
+
+int sift_hip_refine_fundamental(sift_hip_ctx* c, const float* pts, int n_sets, const int64_t* offsets, float threshold, int rounds,
+                                sift_hip_fundamental* models, int32_t* refined, uint8_t* inlier, char* err, int errlen) {
+    if (!c) { match_set_err(err, errlen, "sift_hip_refine_fundamental: no context (the refit runs on the GPU only)"); return SIFT_HIP_EINVAL; }
+    Job j{c, pts, nullptr, n_sets, offsets, nullptr, models, inlier, nullptr, err, errlen};
+    j.refine_only = true;
+    j.fund = true;
+    j.threshold = threshold;
+    j.rounds = rounds;
+    j.refined = refined;
+    return match_guarded(err, errlen, run, &j);
+}
+
+// The refit over the device-resident batch: the coordinates of the records by the gather kernel, then the refit.  The records'
+// indices are checked against the batch before the kernel reads keypoints by them (records in device memory are read back once
+// for that).
+int sift_hip_result_refine_fundamental(sift_hip_ctx* c, int n_pairs, const int32_t* pair_q, const int32_t* pair_t, const sift_hip_match_rec* recs,
+                                       const int32_t* counts, float threshold, int rounds, sift_hip_fundamental* models, int32_t* refined,
+                                       uint8_t* inlier, char* err, int errlen) {
+    const auto bad = [&](const char* what) {
+        match_set_err(err, errlen, (std::string("sift_hip_result_refine_fundamental: ") + what).c_str());
+        return SIFT_HIP_EINVAL;
+    };
+    if (!c) return bad("no context (the refit runs on the GPU only)");
+    if (n_pairs < 0 || (n_pairs > 0 && (!pair_q || !pair_t || !counts || !models))) return bad("bad pair arguments");
+    if (n_pairs == 0) return SIFT_HIP_OK;
+    const MatchCtxView v = match_ctx_view(c);
+    if (!v.have_result) return bad("no batch on the device");
+    std::vector<int> img_row0((size_t)v.n_images + 1, 0);
+    for (int i = 0; i < v.n_images; ++i) img_row0[(size_t)i + 1] = img_row0[(size_t)i] + v.counts[i];
+    std::vector<int64_t> offsets((size_t)n_pairs + 1, 0);
+    std::vector<int> kp_row0((size_t)n_pairs * 2, 0);
+    for (int p = 0; p < n_pairs; ++p) {
+        if (pair_q[p] < 0 || pair_q[p] >= v.n_images || pair_t[p] < 0 || pair_t[p] >= v.n_images) return bad("a pair names an image outside the batch");
+        if (counts[p] < 0) return bad("a negative count");
+        offsets[(size_t)p + 1] = offsets[(size_t)p] + counts[p];
+        kp_row0[2 * (size_t)p] = img_row0[(size_t)pair_q[p]];
+        kp_row0[2 * (size_t)p + 1] = img_row0[(size_t)pair_t[p]];
+    }
+    const int64_t rows = offsets[(size_t)n_pairs];
+    if (rows > 0 && !recs) return bad("no records");
+    if (rows > 0x7fffffffLL / 4) return bad("too many rows");
+    const bool recs_on_device = rows > 0 && match_ptr_on_device(recs);
+    std::vector<sift_hip_match_rec> copy;
+    if (recs_on_device) {
+        copy.resize((size_t)rows);
+        struct Fetch { sift_hip_ctx* c; void* dst; const void* src; size_t bytes; } f{c, copy.data(), recs, (size_t)rows * sizeof(sift_hip_match_rec)};
+        const int rc = match_guarded(err, errlen, [](void* a) {
+            const Fetch& f = *static_cast<const Fetch*>(a);
+            SIFT_HIP_CHECK(hipSetDevice(match_ctx_view(f.c).device));
+            match_download(f.c, f.dst, f.src, f.bytes);
+            return (int)SIFT_HIP_OK;
+        }, &f);
+        if (rc != SIFT_HIP_OK) return rc;
+    }
+    const sift_hip_match_rec* host_recs = recs_on_device ? copy.data() : recs;
+    for (int p = 0; p < n_pairs; ++p)
+        for (int64_t i = offsets[(size_t)p]; i < offsets[(size_t)p + 1]; ++i)
+            if (host_recs[i].query < 0 || host_recs[i].query >= v.counts[pair_q[p]] || host_recs[i].train < 0 || host_recs[i].train >= v.counts[pair_t[p]])
+                return bad("a record names a keypoint outside its image");
+    const Gather g{recs_on_device ? recs : nullptr, v.d_kp, kp_row0.data(), ransac_ctx_subpixel(c) ? 0.5f : 1.0f};
+    Job j{c, nullptr, &g, n_pairs, offsets.data(), nullptr, models, inlier, nullptr, err, errlen};
+    j.refine_only = true;
+    j.fund = true;
+    j.threshold = threshold;
+    j.rounds = rounds;
+    j.refined = refined;
+    j.h_recs = recs_on_device ? nullptr : recs;
     return match_guarded(err, errlen, run, &j);
 }
 

@@ -43,6 +43,16 @@ void launch_fund_score(hipStream_t s, const float* d_pts, const RansacHyp* d_hyp
 void launch_fund_select(hipStream_t s, const RansacHyp* d_hyp, int n_sets, uint32_t slots, int32_t* d_scores, sift_hip_fundamental* d_models);
 void launch_fund_flags(hipStream_t s, const float* d_pts, const int64_t* d_off, int n_sets, long long rows, const sift_hip_fundamental* d_models,
                        float thr2, uint8_t* d_inlier);
+// ---- the refit of F (ransac_fund_refine_math.h).  kFundRefineRows: the rows of a set that the refit kernel keeps in LDS for
+// all its rounds.  2048 rows are 32 KB; with the 2 KB of sums and system a workgroup takes 34 KB of the CU's 160 KB.  The
+// kernel's 190 VGPRs admit two waves a SIMD, i.e. two workgroups a CU (one wave of each per SIMD): 68 KB, so the cap is not
+// what limits occupancy and leaves LDS to other kernels on the CU.  Match lists have hundreds to about a thousand rows.
+constexpr int kFundRefineRows = 2048;
+// `rounds` rounds on every model with iteration >= 0, in place: f and inliers; d_refined (may be null): the rounds accepted per
+// set.  stage_rows: sets of at most that many rows (clamped to 0 .. kFundRefineRows) are staged in LDS - kFundRefineRows but
+// for measurements; the result does not depend on it.
+void launch_fund_refine(hipStream_t s, const float* d_pts, const int64_t* d_off, int n_sets, int rounds, float thr2, int stage_rows,
+                        sift_hip_fundamental* d_models, int32_t* d_refined);
 // rows of sift_hip_result_verify: record i of pair p (d_off: the pairs' record offsets) -> (qx, qy, tx, ty); d_kp_row0: for
 // every pair the first keypoint row of its query image and of its train image (2 ints per pair)
 void launch_ransac_gather(hipStream_t s, const sift_hip_match_rec* d_recs, const int64_t* d_off, int n_pairs, long long rows,

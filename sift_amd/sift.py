@@ -705,6 +705,51 @@ class Context:
             _raise(rc, err)
         return models, inlier
 
+    def refine_fundamental(self, pts, offsets, models, threshold=3.0, rounds=2, refined_out=None, inlier_out=None):
+        """sift_hip_refine_fundamental: at most `rounds` (0 .. 8) rounds of the least-squares refit of given fundamental matrices
+        over their own inliers, no sampling -> (models, refined, inlier); refined[s] = the rounds accepted for set s.  `models`:
+        a FUNDAMENTAL_DTYPE array (copied; f and iteration are read, a model with iteration -1 is left alone), or a tensor /
+        address that is refined in place and returned as given.  `offsets` None: one set (numpy rows only)."""
+        if isinstance(pts, np.ndarray):
+            pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 4)
+        if offsets is None:
+            offsets = [0, pts.shape[0]]
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        n_sets = max(offsets.size - 1, 0)
+        rows = int(offsets[-1]) if offsets.size and offsets[-1] > 0 else 0
+        if isinstance(models, np.ndarray):
+            models = np.array(models, _lib.FUNDAMENTAL_DTYPE).reshape(-1)
+            if models.size != n_sets:
+                raise ValueError("refine_fundamental: one model per set")
+        refined = np.zeros(n_sets, np.int32) if refined_out is None else refined_out
+        inlier = np.zeros(rows, np.uint8) if inlier_out is None else inlier_out
+        err = C.create_string_buffer(512)
+        rc = self._L.sift_hip_refine_fundamental(self._h, self._addr(pts), n_sets, offsets, float(threshold), int(rounds), self._addr(models),
+                                                 self._addr(refined), self._addr(inlier), err, 512)
+        if rc:
+            _raise(rc, err)
+        return models, refined, inlier
+
+    def refine_fundamental_images(self, pairs, recs, counts, models, threshold=3.0, rounds=2):
+        """sift_hip_result_refine_fundamental: refine_fundamental over the last batch, from the records, counts and models that
+        verify_images(model="fundamental") returned for `pairs`; the coordinates are built on the GPU -> (models, refined,
+        inlier), inlier[i] belonging to recs[i]."""
+        pq, pt = self._pairs(pairs)
+        recs = np.ascontiguousarray(recs, _lib.MATCH_DTYPE).reshape(-1)
+        counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
+        models = np.array(models, _lib.FUNDAMENTAL_DTYPE).reshape(-1)
+        if counts.size != pq.size or models.size != pq.size or (counts >= 0).all() and int(counts.sum()) != recs.size:
+            raise ValueError("refine_fundamental_images: one count and one model per pair, and the counts' records")
+        refined = np.zeros(pq.size, np.int32)
+        inlier = np.zeros(recs.size, np.uint8)
+        err = C.create_string_buffer(512)
+        rc = self._L.sift_hip_result_refine_fundamental(self._h, pq.size, pq, pt, C.c_void_p(recs.ctypes.data), counts, float(threshold), int(rounds),
+                                                        C.c_void_p(models.ctypes.data), C.c_void_p(refined.ctypes.data),
+                                                        C.c_void_p(inlier.ctypes.data), err, 512)
+        if rc:
+            _raise(rc, err)
+        return models, refined, inlier
+
     def verify_images(self, pairs, ratio=0.8, cross_check=False, iterations=2048, threshold=3.0, seed=0, refine=0, model="homography",
                       quantized=False):
         """sift_hip_result_verify: match_images followed by ransac_homography on the matches' image coordinates, all on the
@@ -937,6 +982,21 @@ class Sift:
         run = self.ctx.ransac_fundamental if model == "fundamental" else self.ctx.ransac_homography
         models, inlier = run(pts, None, iterations, threshold, seed, refine=refine)
         return recs, models[0], inlier
+
+    def refine_fundamental(self, points_a, points_b, recs, model, threshold: float = 3.0, rounds: int = 2):
+        """The least-squares refit of the record verify(model="fundamental") returned, over its own inliers among `recs` (an
+        extension; Context.refine_fundamental) -> (model, refined, inlier): at most `rounds` (0 .. 8) rounds of which `refined`
+        were accepted; the inlier count never decreases.  Coordinates as verify() forms them."""
+        if "f" not in (getattr(getattr(model, "dtype", None), "names", None) or ()):
+            raise ValueError("refine_fundamental: model must be a record as verify(model=\"fundamental\") returns it")
+        scale = np.float32(0.5 if self.subpixel else 1.0)
+
+        def coords(points, which):
+            xy = np.array([[points[i].loc[0] << points[i].octave, points[i].loc[1] << points[i].octave] for i in which], np.float32)
+            return xy.reshape(-1, 2) * scale
+        pts = np.concatenate([coords(points_a, recs["query"]), coords(points_b, recs["train"])], axis=1)
+        models, refined, inlier = self.ctx.refine_fundamental(pts, None, np.asarray(model).reshape(1), threshold, rounds)
+        return models[0], int(refined[0]), inlier
 
     def match_guided(self, points_a, points_b, model, threshold: float = 3.0, ratio: float = 0.8, cross_check: bool = False):
         """match() again under the model verify() returned (an extension): a point of b competes for a point of a only when it

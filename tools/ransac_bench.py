@@ -28,6 +28,7 @@ APPENDS its lines to --out.
     python tools/ransac_bench.py [--reps 20] [--frames 32] [--out profiles/ransac_bench.txt]
     python tools/ransac_bench.py --refine-arm [--reps 20] [--out profiles/ransac_bench.txt]
     python tools/ransac_bench.py --fundamental-arm [--reps 20] [--out profiles/ransac_bench.txt]
+    python tools/ransac_bench.py --fund-refit-arm [--reps 20] [--out profiles/ransac_bench.txt]
 """
 import argparse
 import json
@@ -57,6 +58,9 @@ def main():
     ap.add_argument("--refine-arm", action="store_true", help="only the refine arm: refine 0 against refine 2, appended to --out")
     ap.add_argument("--fundamental-arm", action="store_true",
                     help="only the fundamental arm: sift_hip_ransac_fundamental against sift_hip_ransac_homography, appended to --out")
+    ap.add_argument("--fund-refit-arm", action="store_true",
+                    help="only the refit arm of F: sift_hip_ransac_fundamental alone against the same call followed by "
+                         "sift_hip_refine_fundamental at 8 rounds, appended to --out")
     args = ap.parse_args()
 
     import torch
@@ -174,6 +178,29 @@ def main():
               "ratio_to_homography": round(fund["median_ms"] / homo["median_ms"], 2),
               "speedup_vs_host_loop": round(host["median_ms"] / fund["median_ms"], 1)})
 
+    def fund_refit_case(name, ctx, pts, off, rounds=8):
+        """sift_hip_ransac_fundamental alone and followed by sift_hip_refine_fundamental, alternating; rows and results on the device."""
+        import fund_refine_ref
+        n_sets = off.size - 1
+        dpts = torch.from_numpy(pts).cuda()
+        dm = torch.zeros((n_sets, 12), dtype=torch.int32, device="cuda")
+        dr = torch.zeros((n_sets,), dtype=torch.int32, device="cuda")
+        df = torch.zeros((max(pts.shape[0], 1),), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+
+        def both():
+            ctx.ransac_fundamental(dpts, off, its, thr, 0, models_out=dm, inlier_out=df)
+            ctx.refine_fundamental(dpts, off, dm, thr, rounds, refined_out=dr, inlier_out=df)
+        plain, fine = race(lambda: ctx.ransac_fundamental(dpts, off, its, thr, 0, models_out=dm, inlier_out=df), both)
+        base = fund_ref.ransac(pts, off, its, thr, 0)
+        want = fund_refine_ref.refine(pts, base[0], off, thr, rounds)
+        ok = (dm.cpu().numpy().tobytes() == want[0].tobytes() and dr.cpu().numpy().tobytes() == want[1].tobytes()
+              and df.cpu().numpy()[:pts.shape[0]].tobytes() == want[2].tobytes())
+        emit({"case": "fundamental refit arm, " + name, "sets": int(n_sets), "rows": int(pts.shape[0]), "iterations": its, "rounds": rounds,
+              "bitwise_equal_to_host_loop": bool(ok), "ransac_alone": plain, "ransac_then_refit": fine,
+              "added_ms_median": round(fine["median_ms"] - plain["median_ms"], 4), "rounds_accepted": want[1].tolist()[:8],
+              "inliers_minimal": base[0]["inliers"].tolist()[:8], "inliers_refitted": want[0]["inliers"].tolist()[:8]})
+
     def finish(mode, header):
         if args.out:
             with open(args.out, mode) as f:
@@ -191,7 +218,9 @@ def main():
     # ---- (a): two 1080p frames' match list ----
     rec, counts = ctx.match_images([(0, 1)], 0.8, False)
     pts = np.concatenate([coords(kp, row0[0], rec["query"]), coords(kp, row0[1], rec["train"])], axis=1)
-    if args.fundamental_arm:
+    if args.fund_refit_arm:
+        fund_case = fund_refit_case
+    if args.fundamental_arm or args.fund_refit_arm:
         fund_case("a: match list of frames 1 and 2 of the bench batch", ctx, pts, np.array([0, pts.shape[0]], np.int64))
         pairs = [(i, i + 1) for i in range(n - 1)]
         rec, counts = ctx.match_images(pairs, 0.8, False)
