@@ -20,6 +20,8 @@ from sift_amd import _lib
 from sift_amd.synthetic import synth_frame
 from test_gpu_parity import CASES, CONVOLVE_SIGMAS, REDUCE_CASES, compare_run, convolve_cases
 from test_scale_steps_host import ROWS, populations, row_image, row_run
+import small_frames
+from test_small_frames_host import COUNTS as SMALL_COUNTS
 
 pytestmark = pytest.mark.gpu
 
@@ -32,6 +34,18 @@ def compare_many_levels(ctx, report_dir, what, frames=1):
     rep = compare_run(ctx, row_image(MANY_LEVELS), dogs, octaves, subpixel, f"{MANY_LEVELS} [{what}]", report_dir, batch_of=frames, sigma=sigma, k=k,
                       run=row_run(MANY_LEVELS))
     assert rep["final"] == final and populations(ctx.stage("final", frames - 1), dogs, octaves, sigma, k) == levels
+
+
+SMALL = ("15x400", "61x31 2oct")    # levels barely longer than the blur radius: no keypoint / two octaves with a 31x16 one (tests/small_frames.py)
+
+
+def compare_small(ctx, report_dir, what, frames=1):
+    """The two small rows through compare_run; candidate and final counts must be the oracle's pinned ones."""
+    for name in SMALL:
+        dogs, octaves, sigma, subpixel = small_frames.ROW[name][5:]
+        rep = compare_run(ctx, small_frames.row_image(name), dogs, octaves, subpixel, f"{name} [{what}]", report_dir, batch_of=frames, sigma=sigma,
+                          run=small_frames.row_run(name))
+        assert (rep["candidates"], rep["final"]) == SMALL_COUNTS[name]
 
 
 def test_this_is_the_diag_library(ctx):
@@ -65,6 +79,7 @@ def test_two_pass_blur_pipeline(ctx, report_dir):
     with forced(ctx, fused_blur=0):
         compare_run(ctx, synth_frame(200, 160, 2), 3, 2, False, "two-pass blur 200x160", report_dir)
         compare_many_levels(ctx, report_dir, "fused_blur = 0")
+        compare_small(ctx, report_dir, "fused_blur = 0")
 
 
 def test_separate_scan_and_edge_filter(ctx, report_dir):
@@ -72,12 +87,14 @@ def test_separate_scan_and_edge_filter(ctx, report_dir):
     aligned get)"""
     with forced(ctx, fused_edge=0):
         compare_run(ctx, synth_frame(320, 250, 4), 3, 3, False, "separate scan / edge filter 320x250", report_dir)
+        compare_small(ctx, report_dir, "fused_edge = 0")
 
 
 def test_separate_blur_and_decimation(ctx, report_dir):
     """reduceToNextLevel as blur -> temporary -> resampling kernel"""
     with forced(ctx, fused_reduce=0):
         compare_run(ctx, synth_frame(1024, 512, 8), 3, 3, False, "separate blur / decimation 1024x512", report_dir, batch_of=4)
+        compare_small(ctx, report_dir, "fused_reduce = 0", frames=2)
 
 
 @pytest.mark.parametrize("case", [REDUCE_CASES[0], REDUCE_CASES[1], REDUCE_CASES[3]], ids=["640x480", "1000x600", "1280x360"])
@@ -103,11 +120,24 @@ def test_dog_levels_written_by_the_pyramid(ctx, report_dir, case, streaming):
         assert rep["final"] > 0
 
 
+@pytest.mark.parametrize("streaming", [0, 1], ids=["tile", "streaming"])
+def test_small_frames_on_the_other_pyramid_forms(ctx, report_dir, streaming):
+    """The small rows with the pyramid writing its DoG levels, with the streaming decimating blur in place of the kept-pixels
+    one, and on one stream: launchers that decline these shapes hand them to the generic path, and parity holds either way."""
+    with forced(ctx, dog_in_extrema=0, stream_min_waves=streaming):
+        compare_small(ctx, report_dir, "dog_in_extrema = 0", frames=2)
+    with forced(ctx, stream_min_waves=streaming, reduce_kept=0):
+        compare_small(ctx, report_dir, "reduce_kept = 0", frames=3)
+    with forced(ctx, pyramid_side=0, stream_min_waves=streaming):
+        compare_small(ctx, report_dir, "pyramid_side = 0")
+
+
 def test_host_glue_path(ctx, report_dir):
     """flags down, libstdc++'s std::sort on the host, lists up (sift.cpp:37-54)"""
     with forced(ctx, gpu_cleanup=0):
         compare_run(ctx, synth_frame(333, 257, 9), 3, 3, False, "host-glue path 333x257", report_dir)
         compare_many_levels(ctx, report_dir, "gpu_cleanup = 0")
+        compare_small(ctx, report_dir, "gpu_cleanup = 0")
 
 
 def test_host_glue_path_with_some_images_throwing(ctx):

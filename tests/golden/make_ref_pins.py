@@ -5,6 +5,7 @@
     python tests/golden/make_ref_pins.py bench_frame | config2 | truncation | configs | config5   (the long-running pins, one fixture each)
     python tests/golden/make_ref_pins.py hard_frames                       (HARD_CASES -> refpin_hard_frames.npz; refpin.npz is not rewritten)
     python tests/golden/make_ref_pins.py scale_steps                       (SCALE_CASES -> refpin_scale_steps.npz; refpin.npz is not rewritten)
+    python tests/golden/make_ref_pins.py small_frames                      (SMALL_CASES -> refpin_small_frames.npz; refpin.npz is not rewritten)
 
 /root/reference/bin/arch_x64/sift cannot be started here (Vigra, OpenCV, Boost are DT_NEEDED and absent) and the
 sources cannot be rebuilt for the same reason, but `Sift::calculate` and the `sift::alg` functions inside it only need
@@ -36,7 +37,7 @@ K_SQRT2 = float(np.float32(np.sqrt(np.float32(2.0))))
 POINT_DTYPE = np.dtype([("x", "<u2"), ("y", "<u2"), ("octave", "<u2"), ("index", "<u2"), ("filtered", "<u2"), ("pad", "<u2"),
                         ("scale", "<f4"), ("orientation", "<f4"), ("n_desc", "<u4")])
 
-# name -> (image spec, dogs, octaves, subpixel).  image spec: ("synth", w, h, seed) | ("parrot",) | ("const", w, h, value) | ("hard", kind, w, h)
+# name -> (image spec, dogs, octaves, subpixel).  image spec: ("synth", w, h, seed) | ("blob", w, h, seed) | ("parrot",) | ("const", w, h, value) | ("hard", kind, w, h)
 CALC_CASES = {
     "synth_200x160_3x2": (("synth", 200, 160, 2), 3, 2, 0),
     "synth_320x250_3x3": (("synth", 320, 250, 4), 3, 3, 0),
@@ -69,6 +70,15 @@ SCALE_CASES = {
     "synth_200x150_3x3_s1.0_k1.8": (("synth", 200, 150, 3), 3, 3, 0, 1.0, 1.8),      # levels (0,0), (0,2) and octave 0's top level (0,3)
 }
 SCALE_PIN = os.path.join(HERE, "refpin_scale_steps.npz")
+# Tiny and thin frames, levels barely longer than the largest blur radius (tests/small_frames.py; the names are its rows'): no
+# keypoint at all, a 19-pixel-wide column, a 17-pixel-high strip whose only legal keypoint row is 8.  A fixture of their own,
+# same keys, and the descriptors in full
+SMALL_CASES = {
+    "15x15": (("synth", 15, 15, 1), 3, 1, 0),
+    "19x257": (("synth", 19, 257, 1), 3, 1, 0),
+    "blob 400x17": (("blob", 400, 17, 3), 3, 1, 0),
+}
+SMALL_PIN = os.path.join(HERE, "refpin_small_frames.npz")
 BLUR_SIGMAS = [0.3, 1.0, 1.6, 2.0, 2.2627418, 3.2, 4.5254836, 6.4]
 BLUR_IMAGES = [("synth", 200, 150, 3), ("synth", 67, 131, 4), ("synth", 64, 64, 5)]
 PARABOLAS = [(3, 1.5, 4, 2.5, 5, 1.0), (0, 0.25, 1, 0.75, 2, 0.5), (34, 12.0, 35, 12.0, 0, 3.0), (10, 1.0, 11, 1.0, 12, 1.0)]
@@ -77,6 +87,8 @@ PARABOLAS = [(3, 1.5, 4, 2.5, 5, 1.0), (0, 0.25, 1, 0.75, 2, 0.5), (34, 12.0, 35
 def make_image(spec):
     if spec[0] == "synth":
         return synth_frame(spec[1], spec[2], spec[3])
+    if spec[0] == "blob":
+        return blob_frame(spec[1], spec[2], spec[3])
     if spec[0] == "const":
         return np.full((spec[2], spec[1]), spec[3], np.float32)
     if spec[0] == "hard":
@@ -138,7 +150,7 @@ def ref_calculate(img, dogs, octaves, subpixel, tmp, sigma=1.6, k=K_SQRT2):
     return res
 
 
-def store_calc(store, name, case, tmp):
+def store_calc(store, name, case, tmp, full_desc=False):
     """One case of a calculate table: what the reference returned for it, into `store` under calc/<name>/."""
     spec, dogs, octaves, sub = case[:4]
     sigma, k = case[4:] if len(case) > 4 else (1.6, K_SQRT2)
@@ -168,6 +180,8 @@ def store_calc(store, name, case, tmp):
     if name == "synth_200x160_3x2":      # one small case in full
         store[f"calc/{name}/desc"] = r["desc"]
         store[f"calc/{name}/levels"] = r["levels"]
+    elif full_desc:
+        store[f"calc/{name}/desc"] = r["desc"]
     print(f"{name}: {r['points'].size} points, {int((r['points']['n_desc'] == 128).sum())} with descriptors")
 
 
@@ -234,6 +248,17 @@ def scale_steps():
             store_calc(store, name, case, tmp)
     np.savez_compressed(SCALE_PIN, **store)
     print("wrote", SCALE_PIN, os.path.getsize(SCALE_PIN), "bytes")
+
+
+def small_frames():
+    assert os.path.exists(REF_BIN), "the reference is not mounted here"
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "_ref/refexec"])
+    store = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for name, case in SMALL_CASES.items():
+            store_calc(store, name, case, tmp, full_desc=True)
+    np.savez_compressed(SMALL_PIN, **store)
+    print("wrote", SMALL_PIN, os.path.getsize(SMALL_PIN), "bytes")
 
 
 def long_running(which):
@@ -314,6 +339,8 @@ if __name__ == "__main__":
         hard_frames()
     elif sys.argv[1:] == ["scale_steps"]:
         scale_steps()
+    elif sys.argv[1:] == ["small_frames"]:
+        small_frames()
     elif len(sys.argv) > 1:
         long_running(sys.argv[1])
     else:

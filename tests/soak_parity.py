@@ -7,8 +7,9 @@ modulo 2 / 4 / 64 / 128, strips that end inside the image, chunks of odd row cou
 reference accepts, batches of 1 - 3 - and, beside the value noise and the blob lattice, the frames of tests/hard_frames.py (negative
 pixels: several orientation peaks and the whole batch redone on the host; two-valued: NaN orientations; plateaus, mirror symmetry,
 periodic patterns, impulses, other value ranges).
-    python3 tests/soak_parity.py [seconds=600] [seed=1] [big]
-("big": shapes 1000..4096 x 700..2200, batches of 1 - 6 - launches large enough to take the streaming kernels by themselves.)
+    python3 tests/soak_parity.py [seconds=600] [seed=1] [big | small]
+("big": shapes 1000..4096 x 700..2200, batches of 1 - 6 - launches large enough to take the streaming kernels by themselves.
+ "small": draw_small() - sides from SMALL_LO..64, levels near the blur radius, thin strips.)
 Prints one line per case and a summary; exits 1 if any case differed.
 """
 import os
@@ -48,6 +49,40 @@ def draw_big(rng):
     return c
 
 
+SMALL_LO = 10     # smallest side draw_small() draws (see its docstring)
+
+
+def draw_small(rng):
+    """Tiny and thin frames (tests/small_frames.py has the fixed rows): w, h from SMALL_LO..64, with probability 0.3 one side
+    replaced by 65..2000 (a strip), one or two octaves, levels barely longer than the plan's largest blur radius - or shorter:
+    the reference then refuses the input and the case counts as skipped.  At most half of the cases may be skipped; with the lower
+    bound SMALL_LO = 10 the oracle alone refuses 138 of the first 300 cases of seed 1 (tests/test_small_frames_host.py checks the cap)."""
+    w, h = int(rng.integers(SMALL_LO, 65)), int(rng.integers(SMALL_LO, 65))
+    if rng.random() < 0.3:
+        long = int(rng.integers(65, 2001))
+        if rng.random() < 0.5:
+            w = long
+        else:
+            h = long
+    octaves = int(rng.integers(1, 3))
+    dogs = int(rng.choice([3, 3, 4, 5]))
+    sigma = float(rng.choice([1.0, 1.6, 1.6, 2.0]))
+    frames = int(rng.integers(1, 4))
+    streaming = int(rng.random() < 0.5)
+    subpixel = bool(rng.random() < 0.1)
+    blobs = bool(rng.random() < 0.1)
+    c = dict(w=w, h=h, dogs=dogs, octaves=octaves, sigma=sigma, subpixel=subpixel, frames=frames, streaming=streaming, blobs=blobs,
+             seed=int(rng.integers(1, 1 << 20)), hard="")
+    c["k"] = float(rng.choice(K_STEPS))      # drawn last, as in draw()
+    return c
+
+
+def case_image(c):
+    if c["hard"]:
+        return GENERATORS[c["hard"]](c["w"], c["h"], c["seed"])
+    return blob_frame(c["w"], c["h"], 3 + c["seed"] % 5) if c["blobs"] else synth_frame(c["w"], c["h"], c["seed"])
+
+
 def draw(rng):
     subpixel = rng.random() < 0.1
     big = rng.random() < 0.25
@@ -78,18 +113,16 @@ def draw(rng):
 def main():
     budget = float(sys.argv[1]) if len(sys.argv) > 1 else 600.0
     rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
-    big = len(sys.argv) > 3 and sys.argv[3] == "big"
+    mode = sys.argv[3] if len(sys.argv) > 3 else ""
+    draw_case = {"big": draw_big, "small": draw_small}.get(mode, draw)
     ctx = Context(0)
     report_dir = tempfile.mkdtemp(prefix="soak_")
     t_end = time.time() + budget
     done, failed, skipped = 0, [], 0
     while time.time() < t_end:
-        c = draw_big(rng) if big else draw(rng)
+        c = draw_case(rng)
         name = "soak %(w)dx%(h)d dogs %(dogs)d oct %(octaves)d sigma %(sigma)g k %(k)g sub %(subpixel)d x%(frames)d stream %(streaming)d blobs %(blobs)d seed %(seed)d %(hard)s" % c
-        if c["hard"]:
-            img = GENERATORS[c["hard"]](c["w"], c["h"], c["seed"])
-        else:
-            img = blob_frame(c["w"], c["h"], 3 + c["seed"] % 5) if c["blobs"] else synth_frame(c["w"], c["h"], c["seed"])
+        img = case_image(c)
         ctx.set_option("stream_min_waves", 1 if c["streaming"] else 0)
         t0 = time.time()
         try:
@@ -107,7 +140,7 @@ def main():
         except Exception:
             failed.append((name, traceback.format_exc().splitlines()[-1]))
             print("FAIL %-110s %s" % (name, failed[-1][1]), flush=True)
-            ctx = Context(0)
+            break      # a library or runtime error, not a mismatch: nothing more is started on a GPU that may have faulted
     print("soak: %d cases bit-identical, %d skipped (the reference refuses the input), %d FAILED" % (done, skipped, len(failed)))
     for name, msg in failed:
         print("  ", name, "::", msg)

@@ -32,13 +32,15 @@ HARD = sorted(G.HARD_CASES)       # tests/hard_frames.py's content, pinned in a 
 HARD_PIN = np.load(G.HARD_PIN)
 SCALE = sorted(G.SCALE_CASES)     # scale steps other than sqrt(2): several gradient levels, pinned in a fixture of their own
 SCALE_PIN = np.load(G.SCALE_PIN)
-ALL_CASES = {**G.CALC_CASES, **G.HARD_CASES, **G.SCALE_CASES}
-assert len(ALL_CASES) == len(CALC) + len(HARD) + len(SCALE)
+SMALL = sorted(G.SMALL_CASES)     # tiny and thin frames (tests/small_frames.py), pinned in a fixture of their own, descriptors in full
+SMALL_PIN = np.load(G.SMALL_PIN)
+ALL_CASES = {**G.CALC_CASES, **G.HARD_CASES, **G.SCALE_CASES, **G.SMALL_CASES}
+assert len(ALL_CASES) == len(CALC) + len(HARD) + len(SCALE) + len(SMALL)
 
 
-@pytest.mark.parametrize("name", CALC + HARD + SCALE)
+@pytest.mark.parametrize("name", CALC + HARD + SCALE + SMALL)
 def test_calculate_matches_the_reference_binary(name):
-    pin = HARD_PIN if name in G.HARD_CASES else SCALE_PIN if name in G.SCALE_CASES else PIN
+    pin = HARD_PIN if name in G.HARD_CASES else SCALE_PIN if name in G.SCALE_CASES else SMALL_PIN if name in G.SMALL_CASES else PIN
     spec, dogs, octaves, sub = ALL_CASES[name][:4]
     sigma, k = ALL_CASES[name][4:] if name in G.SCALE_CASES else (1.6, O.K_SQRT2)
     img = G.make_image(spec)
@@ -98,8 +100,14 @@ def test_calculate_matches_the_reference_binary(name):
     assert checked >= 2 or ref.size == 0
     if name in G.SCALE_CASES:                   # maps of three and four levels, octave 0's top level among them
         assert checked == 2 * {"synth_160x120_5x2_s0.8_k1.5": 4, "synth_200x150_3x3_s1.0_k1.8": 3}[name]
-    if f"calc/{name}/desc" in pin.files:        # the small case stored in full
+    if name in G.SMALL_CASES:                   # the pinned rows are tests/small_frames.py's rows, descriptors bit for bit
+        import small_frames
+        gen, w, h, seed, rdogs, roct, rsigma, rsub = small_frames.ROW[name][1:]
+        assert (spec, dogs, octaves, sub, sigma) == (({synth_frame: "synth", blob_frame: "blob"}[gen], w, h, seed), rdogs, roct, int(rsub), rsigma)
+        assert ref.size == {"15x15": 0, "19x257": 6, "blob 400x17": 25}[name] and pin[f"calc/{name}/desc"].size == 128 * ref.size
+    if f"calc/{name}/desc" in pin.files:        # the small cases stored in full
         assert d.tobytes() == pin[f"calc/{name}/desc"].tobytes()
+    if f"calc/{name}/levels" in pin.files:
         flat = np.concatenate([run.level("gaussian", o, j).reshape(-1) for o in range(mw) for j in range(mh)])
         assert flat.tobytes() == pin[f"calc/{name}/levels"].tobytes()
 
