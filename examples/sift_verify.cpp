@@ -3,7 +3,7 @@
 // or, with model=fundamental, sift::Matcher::verify_fundamental(): a seven-point fundamental matrix, the model for two views of a
 // general scene.  inliers.txt holds the lines of matches.txt that agree with the model.
 //   g++ -std=c++17 -pthread -Iinclude examples/sift_verify.cpp -Lsift_amd/lib -lsift_hip -Wl,-rpath,$PWD/sift_amd/lib -o sift_verify
-//   ./sift_verify a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [refine=0] [model=homography|fundamental] [refit]
+//   ./sift_verify a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [refine=0] [model=homography|fundamental] [refit=-1] [localize=0]
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -37,7 +37,7 @@ static void write_matches(const char* path, const std::vector<sift::Match>& matc
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::cerr << "usage: " << argv[0]
-                  << " a.{pgm,ppm,png,jpg} b.{...} [octaves] [dogsPerEpoch] [ratio] [crossCheck] [iterations] [threshold] [seed] [refine] [homography|fundamental] [refit]\n";
+                  << " a.{pgm,ppm,png,jpg} b.{...} [octaves] [dogsPerEpoch] [ratio] [crossCheck] [iterations] [threshold] [seed] [refine] [homography|fundamental] [refit] [localize]\n";
         return 1;
     }
     const u16_t octaves = argc > 3 ? (u16_t)std::atoi(argv[3]) : 4;
@@ -55,6 +55,8 @@ int main(int argc, char** argv) {
     }
     // with model=fundamental: rounds of the least-squares refit of F (sift::Matcher::refine_fundamental), 0 .. 8; absent: no refit
     const int refit = argc > 12 ? std::atoi(argv[12]) : -1;
+    // 1: the models are estimated on sub-pixel coordinates (sift::Sift::localize after each calculate, sift::Matcher::localize)
+    const bool localize = argc > 13 && std::atoi(argv[13]) != 0;
     if (refit >= 0 && model_name != "fundamental") {
         std::cerr << "refit is for model=fundamental\n";
         return 1;
@@ -66,8 +68,12 @@ int main(int argc, char** argv) {
     try {
         sift::Sift sift(dogsPerEpoch, octaves, 1.6f, std::sqrt(2.0f), false);
         const std::vector<sift::InterestPoint> a = points_of(sift, argv[1]);
+        std::vector<sift_hip_localized> la, lb;
+        if (localize) la = sift.localize();
         const std::vector<sift::InterestPoint> b = points_of(sift, argv[2]);
+        if (localize) lb = sift.localize();
         sift::Matcher matcher;
+        if (localize) matcher.localize(la, lb);
         const std::vector<sift::Match> matches = matcher.match(a, b, ratio, crossCheck);
         if (model_name == "fundamental") {
             sift::Fundamental model = matcher.verify_fundamental(a, b, matches, iterations, threshold, seed, false);

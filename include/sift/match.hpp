@@ -171,7 +171,29 @@ public:
         return out;
     }
 
+    // Sub-pixel coordinates (include/sift_hip.h, "sub-pixel localisation"): from now on verify, verify_fundamental,
+    // refine_fundamental and match_guided take a point's image coordinates from these records - what sift::Sift::localize(max_moves)
+    // returned after the calculate() of the query list and of the train list, one record per point - instead of loc << octave.  A
+    // Matcher holds no pyramid, so the records come from the Sift that made the points.  clear_localize() switches back.
+    void localize(std::vector<sift_hip_localized> query, std::vector<sift_hip_localized> train) {
+        _loc[0] = std::move(query);
+        _loc[1] = std::move(train);
+        _use = true;
+    }
+    void clear_localize() { _use = false; }
+
 private:
+    // the image coordinates of point i of the query (side 0) or train (side 1) list
+    void coords(const InterestPoint& p, int side, size_t i, f32_t scale, f32_t* xy) const {
+        if (_use) {
+            const sift_hip_localized& r = _loc[side].at(i);
+            xy[0] = r.x;
+            xy[1] = r.y;
+        } else {
+            xy[0] = (f32_t)((unsigned)p.loc.x << p.octave) * scale;
+            xy[1] = (f32_t)((unsigned)p.loc.y << p.octave) * scale;
+        }
+    }
     // both lists' descriptor rows and valid flags -> _desc, _kp
     void rows(const std::vector<InterestPoint>& query, const std::vector<InterestPoint>& train) {
         const size_t nq = query.size(), nt = train.size();
@@ -201,9 +223,7 @@ private:
         const f32_t scale = subpixel ? 0.5f : 1.0f;
         _xy.resize((nq + nt) * 2);
         for (size_t i = 0; i < nq + nt; ++i) {   // every point's image coordinates, as gather() forms them per match
-            const InterestPoint& p = i < nq ? query[i] : train[i - nq];
-            _xy[2 * i] = (f32_t)((unsigned)p.loc.x << p.octave) * scale;
-            _xy[2 * i + 1] = (f32_t)((unsigned)p.loc.y << p.octave) * scale;
+            coords(i < nq ? query[i] : train[i - nq], i < nq ? 0 : 1, i < nq ? i : i - nq, scale, &_xy[2 * i]);
         }
         const int64_t offsets[3] = {0, (int64_t)nq, (int64_t)(nq + nt)};
         const int32_t pq = 0, pt = 1;
@@ -228,12 +248,8 @@ private:
         const f32_t scale = subpixel ? 0.5f : 1.0f;
         _pts.resize(matches.size() * 4);
         for (size_t i = 0; i < matches.size(); ++i) {
-            const InterestPoint& q = query.at((size_t)matches[i].query);
-            const InterestPoint& t = train.at((size_t)matches[i].train);
-            _pts[4 * i] = (f32_t)((unsigned)q.loc.x << q.octave) * scale;
-            _pts[4 * i + 1] = (f32_t)((unsigned)q.loc.y << q.octave) * scale;
-            _pts[4 * i + 2] = (f32_t)((unsigned)t.loc.x << t.octave) * scale;
-            _pts[4 * i + 3] = (f32_t)((unsigned)t.loc.y << t.octave) * scale;
+            coords(query.at((size_t)matches[i].query), 0, (size_t)matches[i].query, scale, &_pts[4 * i]);
+            coords(train.at((size_t)matches[i].train), 1, (size_t)matches[i].train, scale, &_pts[4 * i + 2]);
         }
     }
 
@@ -244,6 +260,8 @@ private:
     std::vector<sift_hip_match_rec> _recs;
     std::vector<float> _pts;
     std::vector<float> _xy;                // guided matching: both lists' image coordinates
+    std::vector<sift_hip_localized> _loc[2];   // localize(): the query and the train list's records
+    bool _use = false;
 };
 
 }  // namespace sift

@@ -86,6 +86,18 @@ public:
         if (sift_hip_set_gate(_ctx, gate) != SIFT_HIP_OK) throw std::invalid_argument("sift::Sift::join: gate of another device");
     }
 
+    // Extension (not in the reference): the points the last calculate() returned, moved to the vertex of the 3D quadratic through
+    // their 27 DoG samples (include/sift_hip.h, "sub-pixel localisation"): one record per point, in the points' order; valid for
+    // that calculate() only, whose pyramid they are read from.  sift::Matcher::localize takes them.
+    std::vector<sift_hip_localized> localize(int max_moves = 5) {
+        const long long n = sift_hip_result_total(_ctx);
+        std::vector<sift_hip_localized> recs((size_t)(n > 0 ? n : 0));
+        const int rc = sift_hip_result_localize(_ctx, max_moves, 0, recs.data(), _err, sizeof(_err));
+        if (rc == SIFT_HIP_EINVAL) throw std::invalid_argument(_err);
+        raise(rc);
+        return recs;
+    }
+
 #ifdef SIFT_WITH_VIGRA
     std::vector<InterestPoint> calculate(vigra::MultiArray<2, f32_t>& img) {
         const int w = (int)img.width(), h = (int)img.height();

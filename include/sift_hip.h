@@ -471,6 +471,52 @@ int sift_hip_match_u8(sift_hip_ctx* ctx, const uint8_t* desc, const sift_hip_key
                       int n_pairs, const int32_t* pair_q, const int32_t* pair_t, const sift_hip_match_params* params,
                       sift_hip_match_rec* recs, int32_t* counts, int64_t* total, char* err, int errlen);
 
+/* ---- sub-pixel localisation (an extension) -----------------------------------------------------------------
+ * Every coordinate above is (float)(x << octave): a keypoint of octave 2 sits on a 4-pixel grid of the image.  The reference
+ * solves for the extremum's offset in Sift::_eliminateEdgeResponses (sift.cpp:300-329), uses it for two filter tests and throws
+ * it away; InterestPoint::loc is u16_t.  This call fits the 3D quadratic through the 27 DoG samples around a keypoint and moves
+ * it to the vertex (Lowe 2004, section 4), from the batch's resident pyramid.  sift_amd/csrc/localize_math.h defines every bit
+ * (plain double operations in a fixed order, no fma, no libm); the kernel and a plain host loop (hostmath_localize) compile it.
+ * A stack is the L >= 3 DoG levels of one octave (L = dogs_per_epoch), w x h each; a keypoint is (x, y, i = index).  A step at a
+ * position with 1 <= x <= w - 2, 1 <= y <= h - 2, 1 <= i <= L - 2: the 27 samples d(x + a, y + b, i + c) widened to double (one
+ * not finite: NOT_FINITE); gx = 0.5 * (d(+1,0,0) - d(-1,0,0)), gy, gs likewise; hxx = (d(+1,0,0) + d(-1,0,0)) - (d0 + d0), hyy,
+ * hss likewise; hxy = 0.25 * ((d(+1,+1,0) - d(-1,+1,0)) - (d(+1,-1,0) - d(-1,-1,0))), hxs, hys likewise; det by cofactors along
+ * the first row, minors p * q - r * s, summed left to right (zero or not finite: SINGULAR); off = -(adj(H) g) / det, a component
+ * being one sum of three products in row order, negated, one division (one not finite: NOT_FINITE).  Converged when all three
+ * |o| <= 0.5.  Otherwise every axis steps by +1 where o > 0.5, by -1 where o < -0.5: when max_moves moves have been made the point
+ * ends NOT_CONVERGED, else a new position outside the ranges ends it LEFT_RANGE, else the step repeats there.
+ * The DoG samples are the floats the extremum scan compared: alg::dog of the two Gaussian levels (sift_hip_level_copy kind 1).
+ * Status OK: dx, dy, ds = the offset rounded to float; mx, my, mi = the final sample position minus the keypoint's own; value =
+ * (float)(d0 + 0.5 * ((gx * ox + gy * oy) + gs * os)) there; x = (float)(((double)(kx + mx) + ox) * 2^octave * coord_scale),
+ * coord_scale 0.5 after a subpixel batch and 1 otherwise; y likewise.  Any other status: x, y exactly (float)(x << octave) *
+ * coord_scale, dx, dy, ds +0.0f, mx, my, mi 0, value the centre sample at the keypoint's own position.  moves: the moves made. */
+#define SIFT_HIP_LOCALIZE_OK 0
+#define SIFT_HIP_LOCALIZE_SINGULAR 1
+#define SIFT_HIP_LOCALIZE_NOT_FINITE 2
+#define SIFT_HIP_LOCALIZE_LEFT_RANGE 3
+#define SIFT_HIP_LOCALIZE_NOT_CONVERGED 4
+typedef struct sift_hip_localized {
+    float x, y;           /* image coordinates */
+    float dx, dy, ds;     /* offset from the final sample position, octave pixels / levels */
+    float value;          /* the quadratic's value at the vertex */
+    int16_t mx, my;       /* whole samples moved */
+    int8_t mi;
+    uint8_t status;       /* SIFT_HIP_LOCALIZE_* */
+    uint8_t moves;
+    uint8_t reserved;
+} sift_hip_localized;     /* 32 bytes */
+/* localise every keypoint of the last batch in one launch; out (may be NULL): sift_hip_result_total() records in keypoint
+ * order, host memory or device memory aligned to 16 bytes.  An image that threw has no records.  max_moves 0 .. 8.
+ * use = 1: until the next calculate, the coordinates that sift_hip_result_verify, _verify_fundamental, _refine_fundamental and
+ * _match_guided gather are the records' x, y; use = 0 restores (float)(x << octave).  Every calculate resets use to 0.
+ * SIFT_HIP_EINVAL for max_moves outside 0 .. 8, use above 1 or no results held. */
+int sift_hip_result_localize(sift_hip_ctx* ctx, int max_moves, int use, sift_hip_localized* out, char* err, int errlen);
+/* known-answer entry, like sift_hip_edge_responses: one stack of L host levels back to back, m points (host arrays), the same
+ * device function with octave 0 and coord_scale 1; out: m records, host memory.  SIFT_HIP_EINVAL for L < 3, max_moves outside
+ * 0 .. 8 or a point outside the interior. */
+int sift_hip_localize_points(sift_hip_ctx* ctx, const float* dogs, int L, int w, int h, const uint16_t* xs, const uint16_t* ys,
+                             const uint16_t* is, int m, int max_moves, sift_hip_localized* out, char* err, int errlen);
+
 /* ---- inspection of the last batch (parity tests) ------------------------------------------------ */
 /* kind: 0 gaussian (levels 0..D), 1 dog (0..D-1), 2 magnitude, 3 orientation (initial gradient
  * maps, sift.cpp:130-160, only for levels some keypoint scale selects; 0x0 otherwise). */

@@ -41,6 +41,7 @@ SYMBOLS = [
     "sift_hip_refine_fundamental", "sift_hip_result_refine_fundamental",
     "sift_hip_knn2_guided", "sift_hip_match_guided", "sift_hip_result_match_guided",
     "sift_hip_quantize", "sift_hip_result_copy_u8", "sift_hip_knn2_u8", "sift_hip_match_u8",
+    "sift_hip_result_localize", "sift_hip_localize_points",
 ]
 
 
@@ -71,6 +72,12 @@ HOMOGRAPHY_DTYPE = np.dtype([("h", "<f4", (9,)), ("inliers", "<i4"), ("iteration
 assert HOMOGRAPHY_DTYPE.itemsize == 48
 FUNDAMENTAL_DTYPE = np.dtype([("f", "<f4", (9,)), ("inliers", "<i4"), ("iteration", "<i4"), ("root", "<i4")])
 assert FUNDAMENTAL_DTYPE.itemsize == 48
+
+# sift_hip_localized: a keypoint moved to the vertex of the quadratic through its 27 DoG samples
+LOCALIZED_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("dx", "<f4"), ("dy", "<f4"), ("ds", "<f4"), ("value", "<f4"),
+                            ("mx", "<i2"), ("my", "<i2"), ("mi", "i1"), ("status", "u1"), ("moves", "u1"), ("reserved", "u1")])
+assert LOCALIZED_DTYPE.itemsize == 32
+LOCALIZE_OK, LOCALIZE_SINGULAR, LOCALIZE_NOT_FINITE, LOCALIZE_LEFT_RANGE, LOCALIZE_NOT_CONVERGED = 0, 1, 2, 3, 4
 
 KEYPOINT_DTYPE = np.dtype([("scale", "<f4"), ("orientation", "<f4"), ("x", "<u2"), ("y", "<u2"),
                            ("octave", "<u2"), ("index", "<u2"), ("filtered", "u1"),
@@ -223,5 +230,8 @@ def load():
     L.sift_hip_result_copy_u8.argtypes = [vp, vp]
     L.sift_hip_knn2_u8.argtypes = L.sift_hip_knn2.argtypes
     L.sift_hip_match_u8.argtypes = L.sift_hip_match.argtypes
+    # out: host or device memory
+    L.sift_hip_result_localize.argtypes = [vp, ci, ci, vp, cs, ci]
+    L.sift_hip_localize_points.argtypes = [vp, fp, ci, ci, ci, u16p, u16p, u16p, ci, ci, vp, cs, ci]
     _lib = L
     return L

@@ -4,7 +4,7 @@ overlay :59-76) on top of the GPU path — SURVEY.md §8(f) rows 1-3.
     python -m sift_amd.cli -i image.pgm [-s 1.6] [-k 1.41421354] [-o 4] [-d 3] [-p 0] [-r 1]
     python -m sift_amd.cli -i a.pgm --match b.pgm [--ratio 0.8] [--cross-check]      (an extension: matches.txt)
     python -m sift_amd.cli -i a.pgm --match b.pgm --u8 [--verify ...]                (8-bit descriptors, integer distances)
-    python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--iterations 2048] [--threshold 3] [--seed 0] [--refine 0] [--model homography|fundamental] [--refit N]   (... and inliers.txt)
+    python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--iterations 2048] [--threshold 3] [--seed 0] [--refine 0] [--model homography|fundamental] [--refit N] [--localize]   (... and inliers.txt)
     python -m sift_amd.cli -i a.pgm --match b.pgm --verify --guided [--guided-ratio R]   (... and guided.txt: the matches again, under the verified model)
 
 Image ingest follows Vigra's scalar import: band 0 of multi-band files, values unscaled.  PGM,
@@ -144,6 +144,9 @@ def main(argv=None) -> int:
                          "(two views of a general scene)")
     ap.add_argument("--refit", type=int, default=None, metavar="N",
                     help="with --verify --model fundamental: at most N rounds (0 .. 8) of the least-squares refit of F over its inliers")
+    ap.add_argument("--localize", action="store_true",
+                    help="with --verify: the model is estimated on sub-pixel coordinates, every keypoint moved to the vertex of the "
+                         "quadratic through its 27 DoG samples")
     ap.add_argument("--guided", action="store_true",
                     help="with --verify: match again under the winning model (a point competes only within --threshold pixels of it); "
                          "the matches go to guided.txt")
@@ -154,6 +157,8 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     if args.verify and not args.match:
         ap.error("--verify needs --match")
+    if args.localize and not args.verify:
+        ap.error("--localize needs --verify")
     if args.guided and not args.verify:
         ap.error("--guided needs --verify")
     if args.u8 and not args.match:
@@ -182,6 +187,7 @@ def main(argv=None) -> int:
         img = _load(path)
         sift = Sift(args.dogsPerEpoch, args.octaves, args.sigma, args.k, bool(args.subpixel))
         points = sift.calculate(img)
+        localized = [sift.ctx.localize()] if args.localize else None
         if not args.no_overlay:
             draw_overlay(path, points, sift.subpixel, path + "_orientation.png")
         if args.result:
@@ -189,13 +195,15 @@ def main(argv=None) -> int:
         print(f"{len(points)} interest points")
         if args.match:
             points2 = sift.calculate(_load(args.match))
+            if args.localize:
+                localized.append(sift.ctx.localize())
             if not args.verify:
                 matches = sift.match(points, points2, args.ratio, args.cross_check, args.u8)
             else:
                 matches, model, inlier = sift.verify(points, points2, args.ratio, args.cross_check, args.iterations, args.threshold, args.seed,
-                                                     args.refine, args.model, args.u8)
+                                                     args.refine, args.model, args.u8, localized)
                 if args.refit is not None:
-                    model, refitted, inlier = sift.refine_fundamental(points, points2, matches, model, args.threshold, args.refit)
+                    model, refitted, inlier = sift.refine_fundamental(points, points2, matches, model, args.threshold, args.refit, localized)
             write_matches("matches.txt", matches)
             print(f"{len(points2)} interest points in {args.match}, {len(matches)} matches")
             if args.verify:
@@ -218,7 +226,7 @@ def main(argv=None) -> int:
                         print("H " + " ".join("%.9g" % float(v) for v in model["h"][3 * r:3 * r + 3]))
                 if args.guided:   # no winner: the all-zero model admits nothing, the file is empty
                     ratio = args.ratio if args.guided_ratio is None else args.guided_ratio
-                    guided = sift.match_guided(points, points2, model, args.threshold, ratio, args.cross_check)
+                    guided = sift.match_guided(points, points2, model, args.threshold, ratio, args.cross_check, localized)
                     write_matches("guided.txt", guided)
                     print(f"{len(guided)} guided matches -> guided.txt")
     except (PreconditionViolation, AssertionError, RuntimeError, OSError) as ex:  # main.cpp:90-92

@@ -256,6 +256,18 @@ void launch_descriptors_wave(hipStream_t s, const DevPlan* d_plan, const DevPlan
                              float* d_desc_out, long long out_cap, int dbg = 0, int* d_wire_sums = nullptr, hipEvent_t ev_start = nullptr,
                              hipEvent_t ev_stop = nullptr);
 
+// sub-pixel localisation (kernels_localize.hip; the definition: localize_math.h).  One launch for all keypoints of the batch:
+// d_img_row0 holds n_images + 1 row offsets of the images' keypoints; from_gauss: the plan holds Gaussian levels only; d_xy
+// (two floats per keypoint) receives the records' x, y
+void launch_localize_batch(hipStream_t s, const DevPlan* d_plan, bool from_gauss, const sift_hip_keypoint* d_kp, const int* d_img_row0, int n_images,
+                           long long rows, int max_moves, float coord_scale, sift_hip_localized* d_out, float* d_xy);
+void launch_localize_points(hipStream_t s, const float* d_dogs, int L, int w, int h, const uint16_t* d_xs, const uint16_t* d_ys, const uint16_t* d_is,
+                            int m, int max_moves, sift_hip_localized* d_out);
+// launch_ransac_gather's variant that reads the keypoints' points from d_xy instead of forming (float)(x << octave)
+void launch_localize_gather(hipStream_t s, const sift_hip_match_rec* d_recs, const int64_t* d_off, int n_pairs, long long rows, const float* d_xy,
+                            const int* d_kp_row0, float* d_pts);
+void tu_touch_localize(hipStream_t s);
+
 // wire format of the keypoint gather (kernels_wire.hip)
 size_t wire_blocks(long long total);
 void launch_wire_unpack(hipStream_t s, const uint8_t* d_records, const float* d_values, long long total, int* d_sums,

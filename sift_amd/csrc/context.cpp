@@ -208,6 +208,10 @@ struct sift_hip_ctx {
     long long prof_batches = 0;           // batches whose launches carried the events since the last reset
     sift_hip::MatchState* match_state = nullptr;   // the matcher's scratch (match.cpp), made by the first match call
     sift_hip::RansacState* ransac_state = nullptr; // the same for the geometric verification (ransac.cpp)
+    // sub-pixel localisation (sift_hip_result_localize): the records and their (x, y) of the last batch, the images' row offsets
+    DevBuf d_loc, d_loc_xy, d_loc_row0;
+    HostBuf h_loc_row0;               // page-locked image of the row offsets (every call ends in a wait, so it is free again)
+    bool loc_use = false;             // the gathering result calls read d_loc_xy; every calculate resets it
 };
 
 namespace {
@@ -1129,6 +1133,7 @@ int run_batch(sift_hip_ctx* c, const float* d_in, char* err, int errlen) {
     c->wire_values = c->wire_for_total = -1;
     c->wire_counted = false;
     c->wire_scanned = false;
+    c->loc_use = false;
     c->profile = c->profile_every > 0 && (c->profile_batches++ % c->profile_every) == 0;
     if (c->profile) c->prof_batches++;
 
@@ -1294,6 +1299,7 @@ int match_guarded(char* err, int errlen, int (*fn)(void*), void* arg) { return g
 void match_set_err(char* err, int errlen, const char* msg) { set_err(err, errlen, msg); }
 RansacState** ransac_ctx_state(sift_hip_ctx* c) { return &c->ransac_state; }
 bool ransac_ctx_subpixel(sift_hip_ctx* c) { return c->plan.params.subpixel != 0; }
+const float* localize_ctx_xy(sift_hip_ctx* c) { return (c->have_result && c->loc_use) ? c->d_loc_xy.as<float>() : nullptr; }
 }  // namespace sift_hip
 
 // =====================================================================================================
@@ -1342,6 +1348,7 @@ int sift_hip_create(int device, sift_hip_ctx** out, char* err, int errlen) {
                 tu_touch_pyramid(c->stream); tu_touch_pair(c->stream); tu_touch_reduce(c->stream); tu_touch_extrema(c->stream); tu_touch_orient(c->stream);
                 tu_touch_desc(c->stream); tu_touch_cleanup(c->stream); tu_touch_wire(c->stream); tu_touch_io(c->stream);
                 tu_touch_match(c->stream);
+                tu_touch_localize(c->stream);
                 SIFT_HIP_CHECK(hipGetLastError());
                 SIFT_HIP_CHECK(hipStreamSynchronize(c->stream));
                 touched[device] = true;
@@ -1362,9 +1369,10 @@ void sift_hip_destroy(sift_hip_ctx* c) {
     ApiGuard api;
     for (DevBuf* b : {&c->arena, &c->d_plan, &c->d_taps, &c->d_luts, &c->d_taps16, &c->d_input, &c->d_input_u8, &c->d_sparse_rec, &c->d_sparse_val, &c->d_base, &c->d_tmp, &c->d_tmp2,
                       &c->d_wk, &c->d_wi, &c->d_wi2, &c->d_wp, &c->d_status, &c->d_pool, &c->d_order, &c->d_masks, &c->d_fmasks, &c->d_counts, &c->d_tile_counts, &c->d_totals, &c->d_cands, &c->d_flags, &c->d_list, &c->d_list_cnt, &c->d_orient,
-                      &c->d_peaks, &c->d_final, &c->d_final_cnt, &c->d_out_base, &c->d_kp, &c->d_desc, &c->d_lrank, &c->d_ochunk, &c->d_ocnt, &c->d_recs, &c->d_wire_sums, &c->d_wire_off, &c->d_unpack_sums, &c->d_unpack_off, &c->d_cell_cnt, &c->d_cell_off})
+                      &c->d_peaks, &c->d_final, &c->d_final_cnt, &c->d_out_base, &c->d_kp, &c->d_desc, &c->d_lrank, &c->d_ochunk, &c->d_ocnt, &c->d_recs, &c->d_wire_sums, &c->d_wire_off, &c->d_unpack_sums, &c->d_unpack_off, &c->d_cell_cnt, &c->d_cell_off,
+                      &c->d_loc, &c->d_loc_xy, &c->d_loc_row0})
         b->release();
-    for (HostBuf* b : {&c->h_flags, &c->h_orient, &c->h_peaks, &c->h_status, &c->h_wire, &c->h_stage[0], &c->h_stage[1]}) b->release();
+    for (HostBuf* b : {&c->h_flags, &c->h_orient, &c->h_peaks, &c->h_status, &c->h_wire, &c->h_stage[0], &c->h_stage[1], &c->h_loc_row0}) b->release();
     for (auto& e : c->ev_stage) if (e) (void)hipEventDestroy(e);
     for (auto& p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
@@ -2152,6 +2160,78 @@ int sift_hip_edge_responses(sift_hip_ctx* c, const float* dog0, const float* dog
         launch_edge_filter_points(c->stream, a, b, d, w, h, dx, dy, m, df);
         SIFT_HIP_CHECK(hipStreamSynchronize(c->stream));
         SIFT_HIP_CHECK(hipMemcpy(flags, df, (size_t)m, hipMemcpyDeviceToHost));
+        return SIFT_HIP_OK;
+    });
+}
+
+// ---- sub-pixel localisation (kernels_localize.hip; the definition: localize_math.h) ----
+int sift_hip_localize_points(sift_hip_ctx* c, const float* dogs, int L, int w, int h, const uint16_t* xs, const uint16_t* ys, const uint16_t* is, int m,
+                             int max_moves, sift_hip_localized* out, char* err, int errlen) {
+    const auto bad = [&](const char* what) {
+        set_err(err, errlen, std::string("sift_hip_localize_points: ") + what);
+        return SIFT_HIP_EINVAL;
+    };
+    if (!c) return bad("no context (the localisation runs on the GPU only)");
+    if (max_moves < 0 || max_moves > 8) return bad("max_moves must be 0 .. 8");
+    if (L < 3 || L > 32767 || w < 3 || h < 3 || w >= 32768 || h >= 32768 || m < 0) return bad("a stack has L >= 3 levels of at least 3 x 3");
+    if (!dogs || (m > 0 && (!xs || !ys || !is || !out))) return bad("a null argument");
+    for (int k = 0; k < m; ++k)
+        if (xs[k] < 1 || xs[k] > w - 2 || ys[k] < 1 || ys[k] > h - 2 || is[k] < 1 || is[k] > L - 2) return bad("a point outside the interior of the stack");
+    if (m == 0) return SIFT_HIP_OK;
+    return guarded(err, errlen, [&]() {
+        SIFT_HIP_CHECK(hipSetDevice(c->device));
+        Scratch s;
+        float* d = s.upload(dogs, (size_t)L * (size_t)w * (size_t)h);
+        uint16_t* dx = s.upload(xs, (size_t)m);
+        uint16_t* dy = s.upload(ys, (size_t)m);
+        uint16_t* di = s.upload(is, (size_t)m);
+        sift_hip_localized* dr = s.dev<sift_hip_localized>((size_t)m);
+        launch_localize_points(c->stream, d, L, w, h, dx, dy, di, m, max_moves, dr);
+        SIFT_HIP_CHECK(hipGetLastError());
+        SIFT_HIP_CHECK(hipStreamSynchronize(c->stream));
+        SIFT_HIP_CHECK(hipMemcpy(out, dr, (size_t)m * sizeof(sift_hip_localized), hipMemcpyDeviceToHost));
+        return SIFT_HIP_OK;
+    });
+}
+
+int sift_hip_result_localize(sift_hip_ctx* c, int max_moves, int use, sift_hip_localized* out, char* err, int errlen) {
+    const auto bad = [&](const char* what) {
+        set_err(err, errlen, std::string("sift_hip_result_localize: ") + what);
+        return SIFT_HIP_EINVAL;
+    };
+    if (!c) return bad("no context (the localisation runs on the GPU only)");
+    if (max_moves < 0 || max_moves > 8) return bad("max_moves must be 0 .. 8");
+    if (use < 0 || use > 1) return bad("use must be 0 or 1");
+    if (!c->have_result || !c->have_pyramid) return bad("the context holds no results");
+    const bool out_direct = out && match_ptr_on_device(out);
+    if (out_direct && (reinterpret_cast<uintptr_t>(out) & 15u) != 0) return bad("records in device memory must be 16-byte aligned");
+    return guarded(err, errlen, [&]() {
+        SIFT_HIP_CHECK(hipSetDevice(c->device));
+        const Plan& P = c->plan;
+        const int n = (int)c->counts.size();
+        const long long rows = c->total;
+        if (rows > 0) {
+            // every Gaussian level of every octave has a carve of its own in the arena (build_plan) and nothing rewrites one before
+            // the next calculate, so the four levels around a DoG index are still the ones the extremum scan read
+            // (the context's own per-image bases, d_out_base, are long long and are written by either the host or the descriptor
+            // grid kernel depending on the path; the n + 1 ints here go through a page-locked buffer, so no wait precedes the launch)
+            const size_t row0_bytes = ((size_t)n + 1) * sizeof(int);
+            c->h_loc_row0.ensure(row0_bytes);
+            int* row0 = c->h_loc_row0.as<int>();
+            row0[0] = 0;
+            for (int i = 0; i < n; ++i) row0[i + 1] = row0[i] + c->counts[(size_t)i];
+            c->d_loc_row0.ensure(row0_bytes);
+            c->d_loc_xy.ensure((size_t)rows * 2 * sizeof(float));
+            if (!out_direct) c->d_loc.ensure((size_t)rows * sizeof(sift_hip_localized));
+            SIFT_HIP_CHECK(hipMemcpyAsync(c->d_loc_row0.p, row0, row0_bytes, hipMemcpyHostToDevice, c->stream));
+            sift_hip_localized* d_out = out_direct ? out : c->d_loc.as<sift_hip_localized>();
+            launch_localize_batch(c->stream, c->d_plan.as<DevPlan>(), c->dogs_missing, c->d_kp.as<sift_hip_keypoint>(), c->d_loc_row0.as<int>(), n, rows,
+                                  max_moves, P.params.subpixel ? 0.5f : 1.0f, d_out, c->d_loc_xy.as<float>());
+            SIFT_HIP_CHECK(hipGetLastError());
+            if (out && !out_direct) download(c, out, d_out, (size_t)rows * sizeof(sift_hip_localized), c->stream);
+            wait_stream(c, c->stream);
+        }
+        c->loc_use = use != 0;
         return SIFT_HIP_OK;
     });
 }

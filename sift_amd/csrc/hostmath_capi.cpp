@@ -12,6 +12,7 @@
 #include "ransac_math.h"
 #include "ransac_refine_math.h"
 #include "ransac_fund_refine_math.h"
+#include "localize_math.h"
 #include "../../include/sift_hip.h"   // sift_hip_homography, sift_hip_fundamental
 
 extern "C" {
@@ -547,5 +548,22 @@ int hostmath_fund_refine_sums(const float* pts, long long m, const float* f, flo
     for (int k = 0; k < 36; ++k) out[k] = S36[k];
     norm[0] = nm.cqx; norm[1] = nm.cqy; norm[2] = nm.sq; norm[3] = nm.ctx; norm[4] = nm.cty; norm[5] = nm.st;
     return n;
+}
+}
+
+// ---- sub-pixel localisation (localize_math.h): the plain loop ---------------------------------------------------
+extern "C" {
+// m points of one stack of L levels back to back (w x h each), every point inside the interior; octave and coord_scale as the
+// batch call passes them (0 and 1.0f for sift_hip_localize_points)
+void hostmath_localize(const float* dogs, int L, int w, int h, const uint16_t* xs, const uint16_t* ys, const uint16_t* is, int m, int max_moves,
+                       int octave, float coord_scale, sift_hip_localized* out) {
+    using namespace sift_hip;
+    const size_t px = (size_t)w * (size_t)h;
+    const auto fetch = [&](int x, int y, int i, float (&s)[27]) {
+        for (int c = -1; c <= 1; ++c)
+            for (int b = -1; b <= 1; ++b)
+                for (int a = -1; a <= 1; ++a) s[9 * (c + 1) + 3 * (b + 1) + (a + 1)] = dogs[(size_t)(i + c) * px + (size_t)(y + b) * (size_t)w + (size_t)(x + a)];
+    };
+    for (int k = 0; k < m; ++k) out[k] = localize_point(fetch, w, h, L, xs[k], ys[k], is[k], max_moves, octave, coord_scale);
 }
 }

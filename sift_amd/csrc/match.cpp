@@ -68,6 +68,7 @@ struct Job {
     const sift_hip_guide_params* guide = nullptr;
     const float* models = nullptr;
     float coord_scale = 1.0f;   // the result call's: 0.5f after a batch with subpixel
+    const float* ctx_xy = nullptr;   // the result call's after sift_hip_result_localize with use = 1: the points, already built
     const uint8_t* desc8 = nullptr;   // sift_hip_knn2_u8 / sift_hip_match_u8: byte rows in place of `desc`
     bool is_u8 = false;
 };
@@ -192,7 +193,9 @@ int run(void* arg) {
     if (j.guided) {
         ga.thr2 = j.guide->threshold * j.guide->threshold;
         ga.xy = j.xy;
-        if (j.inputs_on_device) {   // the context's keypoints: every row's point is built on the device
+        if (j.inputs_on_device && j.ctx_xy) {
+            ga.xy = j.ctx_xy;
+        } else if (j.inputs_on_device) {   // the context's keypoints: every row's point is built on the device
             st.d_xy.ensure((size_t)rows * 2 * sizeof(float));
             launch_match_coords(v.stream, d_kp, rows, j.coord_scale, st.d_xy.as<float>());
             ga.xy = st.d_xy.as<float>();
@@ -401,6 +404,7 @@ static int result_match_guided(sift_hip_ctx* c, int n_pairs, const int32_t* pair
     j.guide = guide;
     j.models = models;
     j.coord_scale = ransac_ctx_subpixel(c) ? 0.5f : 1.0f;
+    j.ctx_xy = localize_ctx_xy(c);
     return match_guarded(err, errlen, run, &j);
 }
 

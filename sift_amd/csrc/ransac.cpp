@@ -57,6 +57,7 @@ struct Gather {
     const sift_hip_keypoint* d_kp;
     const int* kp_row0;   // host: 2 ints per pair
     float coord_scale;
+    const float* d_xy;    // sift_hip_result_localize with use = 1: the keypoints' points are read from here; else null
 };
 struct Job {
     sift_hip_ctx* c;
@@ -194,7 +195,9 @@ int run(void* arg) {
     int32_t* d_refined = !j.refined ? nullptr : (refined_direct ? j.refined : st.d_refined.as<int32_t>());
 
     // ---- the launches: one of each kernel, whatever the number of sets ----
-    if (j.gather)
+    if (j.gather && gather_dev.d_xy)
+        launch_localize_gather(v.stream, gather_dev.d_recs, st.d_off.as<int64_t>(), j.n_sets, rows, gather_dev.d_xy, st.d_kp_row0.as<int>(), st.d_pts.as<float>());
+    else if (j.gather)
         launch_ransac_gather(v.stream, gather_dev.d_recs, st.d_off.as<int64_t>(), j.n_sets, rows, gather_dev.d_kp, st.d_kp_row0.as<int>(),
                              gather_dev.coord_scale, st.d_pts.as<float>());
     if (j.refine_only) {
@@ -311,7 +314,7 @@ int sift_hip_result_refine_fundamental(sift_hip_ctx* c, int n_pairs, const int32
         for (int64_t i = offsets[(size_t)p]; i < offsets[(size_t)p + 1]; ++i)
             if (host_recs[i].query < 0 || host_recs[i].query >= v.counts[pair_q[p]] || host_recs[i].train < 0 || host_recs[i].train >= v.counts[pair_t[p]])
                 return bad("a record names a keypoint outside its image");
-    const Gather g{recs_on_device ? recs : nullptr, v.d_kp, kp_row0.data(), ransac_ctx_subpixel(c) ? 0.5f : 1.0f};
+    const Gather g{recs_on_device ? recs : nullptr, v.d_kp, kp_row0.data(), ransac_ctx_subpixel(c) ? 0.5f : 1.0f, localize_ctx_xy(c)};
     Job j{c, nullptr, &g, n_pairs, offsets.data(), nullptr, models, inlier, nullptr, err, errlen};
     j.refine_only = true;
     j.fund = true;
@@ -354,7 +357,7 @@ static int result_verify(bool fund, sift_hip_ctx* c, int n_pairs, const int32_t*
         kp_row0[2 * (size_t)p] = img_row0[(size_t)pair_q[p]];       // the indices passed the matcher's check
         kp_row0[2 * (size_t)p + 1] = img_row0[(size_t)pair_t[p]];
     }
-    const Gather g{d_recs, v.d_kp, kp_row0.data(), ransac_ctx_subpixel(c) ? 0.5f : 1.0f};
+    const Gather g{d_recs, v.d_kp, kp_row0.data(), ransac_ctx_subpixel(c) ? 0.5f : 1.0f, localize_ctx_xy(c)};
     Job j{c, nullptr, &g, n_pairs, offsets.data(), ransac_params, models, inlier, nullptr, err, errlen};
     j.fund = fund;
     return match_guarded(err, errlen, run, &j);

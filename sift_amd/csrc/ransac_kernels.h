@@ -63,6 +63,8 @@ struct RansacState;                        // scratch, owned by the context once
 void ransac_state_free(RansacState* st);   // ransac.cpp; sift_hip_destroy calls it
 RansacState** ransac_ctx_state(sift_hip_ctx* c);
 bool ransac_ctx_subpixel(sift_hip_ctx* c);   // did the last batch run with subpixel (coordinates of the doubled image)?
+// two floats per keypoint of the last batch when sift_hip_result_localize switched the gathers to its records (use = 1); else null
+const float* localize_ctx_xy(sift_hip_ctx* c);
 
 // ---- the matcher as ransac.cpp sees it (match.cpp) ----
 // sift_hip_result_match that also leaves its list on the device: *d_recs = the dense records (device memory: the matcher's

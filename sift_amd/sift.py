@@ -265,6 +265,10 @@ class Context:
             raise HipError("sift_hip_level_copy failed")
         return out
 
+    def dog_stack(self, octave: int, dogs: int, image: int = 0):
+        """The `dogs` DoG levels of one octave of one image as one array [dogs, h, w]: the stack localize() reads."""
+        return np.stack([self.level("dog", octave, j, image) for j in range(dogs)])
+
     def level_scale(self, kind: str, octave: int, level: int) -> float:
         return float(self._L.sift_hip_level_scale(self._h, KINDS[kind], octave, level))
 
@@ -323,6 +327,36 @@ class Context:
         if self._L.sift_hip_edge_responses(self._h, d0, d1, d2, d0.shape[1], d0.shape[0], xs, ys, xs.size, flags):
             raise HipError("sift_hip_edge_responses failed")
         return flags
+
+    # ---- sub-pixel localisation (include/sift_hip.h, "sub-pixel localisation") -------------------------
+    def localize(self, max_moves=5, use=False, out=None):
+        """sift_hip_result_localize: every keypoint of the last batch moved to the vertex of the 3D quadratic through its 27 DoG
+        samples, in one launch -> LOCALIZED_DTYPE records in keypoint order (x, y: image coordinates; status 0: moved).  `use`:
+        until the next calculate, verify_images, refine_fundamental_images and match_images_guided gather these x, y instead of
+        (float)(x << octave).  `out`: a numpy array, a tensor or an address (host or device memory) that receives the records and
+        is returned as given."""
+        total = max(self.total(), 0) if self._L.sift_hip_result_images(self._h) >= 0 else 0   # no results: the call says so
+        recs = np.zeros(total, _lib.LOCALIZED_DTYPE) if out is None else out
+        err = C.create_string_buffer(512)
+        rc = self._L.sift_hip_result_localize(self._h, int(max_moves), int(use), self._addr(recs), err, 512)
+        if rc:
+            _raise(rc, err)
+        return recs
+
+    def localize_points(self, dogs, xs, ys, indices, max_moves=5):
+        """sift_hip_localize_points: the same device function over one stack `dogs` [L, h, w] and the points (xs, ys, indices)
+        -> LOCALIZED_DTYPE records (octave 0, coordinates unscaled)."""
+        dogs = np.ascontiguousarray(dogs, np.float32)
+        xs, ys, indices = (np.ascontiguousarray(a, np.uint16).reshape(-1) for a in (xs, ys, indices))
+        if dogs.ndim != 3 or not (xs.size == ys.size == indices.size):
+            raise ValueError("localize_points: dogs is [L, h, w]; one x, y and index per point")
+        out = np.zeros(xs.size, _lib.LOCALIZED_DTYPE)
+        err = C.create_string_buffer(512)
+        rc = self._L.sift_hip_localize_points(self._h, dogs, dogs.shape[0], dogs.shape[2], dogs.shape[1], xs, ys, indices, xs.size, int(max_moves),
+                                              C.c_void_p(out.ctypes.data), err, 512)
+        if rc:
+            _raise(rc, err)
+        return out
 
     def vertex_parabola(self, lnx, lny, px, py, rnx, rny):
         a = [np.ascontiguousarray(v, np.uint16) for v in (lnx, px, rnx)]
@@ -607,10 +641,13 @@ class Context:
         return self.match_guided_sets(desc, xy, offsets, [(0, 1)], np.asarray(model_matrix, np.float32).reshape(1, 9), model, threshold, ratio,
                                       cross_check, kp)[0]
 
-    def match_images_guided(self, pairs, models, model="homography", threshold=3.0, ratio=0.8, cross_check=False, quantized=False):
+    def match_images_guided(self, pairs, models, model="homography", threshold=3.0, ratio=0.8, cross_check=False, quantized=False,
+                            localized=False):
         """sift_hip_result_match_guided: match_images under the pairs' models, e.g. those verify_images returned, on the
         device-resident results (the keypoints' image coordinates are built on the GPU) -> (records, counts).  `quantized=True`
-        is a ValueError, as for match_guided_sets."""
+        is a ValueError, as for match_guided_sets.  `localized`: localize(use=True) first - the points are the sub-pixel ones."""
+        if localized:
+            self.localize(use=True)
         pq, pt = self._pairs(pairs)
         cnt = self.counts() if self._L.sift_hip_result_images(self._h) >= 0 else np.zeros(0, np.int32)   # none: the call says so
         rows = int(sum(cnt[q] for q in pq if 0 <= q < cnt.size))
@@ -730,10 +767,12 @@ class Context:
             _raise(rc, err)
         return models, refined, inlier
 
-    def refine_fundamental_images(self, pairs, recs, counts, models, threshold=3.0, rounds=2):
+    def refine_fundamental_images(self, pairs, recs, counts, models, threshold=3.0, rounds=2, localized=False):
         """sift_hip_result_refine_fundamental: refine_fundamental over the last batch, from the records, counts and models that
         verify_images(model="fundamental") returned for `pairs`; the coordinates are built on the GPU -> (models, refined,
-        inlier), inlier[i] belonging to recs[i]."""
+        inlier), inlier[i] belonging to recs[i].  `localized`: localize(use=True) first - sub-pixel coordinates."""
+        if localized:
+            self.localize(use=True)
         pq, pt = self._pairs(pairs)
         recs = np.ascontiguousarray(recs, _lib.MATCH_DTYPE).reshape(-1)
         counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
@@ -751,14 +790,17 @@ class Context:
         return models, refined, inlier
 
     def verify_images(self, pairs, ratio=0.8, cross_check=False, iterations=2048, threshold=3.0, seed=0, refine=0, model="homography",
-                      quantized=False):
+                      quantized=False, localized=False):
         """sift_hip_result_verify: match_images followed by ransac_homography on the matches' image coordinates, all on the
         device-resident results -> (records, counts, models, inlier): models[p] belongs to pair p, inlier[i] to records[i].
         `refine` as for ransac_homography.  model="fundamental": sift_hip_result_verify_fundamental, ransac_fundamental in
-        place of ransac_homography (models of FUNDAMENTAL_DTYPE; `refine` must be 0).  `quantized` as for match_images."""
+        place of ransac_homography (models of FUNDAMENTAL_DTYPE; `refine` must be 0).  `quantized` as for match_images.
+        `localized`: localize(use=True) first - the coordinates are the sub-pixel ones of the localisation records."""
         if model not in ("homography", "fundamental"):
             raise ValueError('verify_images: model must be "homography" or "fundamental"')
         fund = model == "fundamental"
+        if localized:
+            self.localize(use=True)
         pq, pt = self._pairs(pairs)
         cnt = self.counts() if self._L.sift_hip_result_images(self._h) >= 0 else np.zeros(0, np.int32)   # none: the call says so
         rows = int(sum(cnt[q] for q in pq if 0 <= q < cnt.size))
@@ -946,6 +988,17 @@ class Sift:
         kp, desc = self.ctx.results()
         return self.ctx.counts(), kp, desc
 
+    def _coords(self, points, which, localized, side):
+        """Image coordinates [len(which), 2] of points[which]: loc * 2^octave (halved with subpixel), or the x, y of the side's
+        records when `localized` is a pair of LOCALIZED_DTYPE arrays (Context.localize() after the calculate() of each list)."""
+        which = np.asarray(which, np.int64)
+        if localized is not None:
+            if len(localized) != 2 or len(localized[side]) != len(points):
+                raise ValueError("localized is a pair of record arrays, one record per point")
+            return np.stack([localized[side]["x"][which], localized[side]["y"][which]], axis=1).astype(np.float32).reshape(-1, 2)
+        xy = np.array([[points[i].loc[0] << points[i].octave, points[i].loc[1] << points[i].octave] for i in which], np.float32)
+        return xy.reshape(-1, 2) * np.float32(0.5 if self.subpixel else 1.0)
+
     def match(self, points_a, points_b, ratio: float = 0.8, cross_check: bool = False, quantized: bool = False):
         """Matches between two InterestPoint lists (an extension: the reference has no matcher) -> records (query, train,
         dist2, second2), indices into the lists.  A point without a 128-float descriptor is an invalid row.  `quantized`: the
@@ -963,62 +1016,51 @@ class Sift:
         return self.ctx.match(qa, qb, ratio, cross_check, ka, kb, quantized)
 
     def verify(self, points_a, points_b, ratio: float = 0.8, cross_check: bool = False, iterations: int = 2048, threshold: float = 3.0,
-               seed: int = 0, refine: int = 0, model: str = "homography", quantized: bool = False):
+               seed: int = 0, refine: int = 0, model: str = "homography", quantized: bool = False, localized=None):
         """match() followed by the geometric check of its list (an extension) -> (records, model, inlier): the best four-point
         homography from image a to image b over the matches' image coordinates (loc * 2^octave, halved with subpixel), as one
         record (h [9] row-major, inliers, iteration; -1: none, refined), and one flag per record.  `refine`: rounds of
         least-squares re-estimation over the inliers, 0 .. 8 (0: the minimal-sample model).  model="fundamental": the best
         seven-point fundamental matrix instead, (tb, 1) F (ta, 1)^T = 0, as one record (f [9], inliers, iteration, root); the
-        right model for two views of a general scene, where a homography explains one plane only.  `refine` must then be 0."""
+        right model for two views of a general scene, where a homography explains one plane only.  `refine` must then be 0.
+        `localized`: a pair of LOCALIZED_DTYPE arrays, the records ctx.localize() returned after the calculate() of each list;
+        the coordinates are then the records' sub-pixel x, y."""
         if model not in ("homography", "fundamental"):
             raise ValueError('verify: model must be "homography" or "fundamental"')
         recs = self.match(points_a, points_b, ratio, cross_check, quantized)
-        scale = np.float32(0.5 if self.subpixel else 1.0)
-
-        def coords(points, which):
-            xy = np.array([[points[i].loc[0] << points[i].octave, points[i].loc[1] << points[i].octave] for i in which], np.float32)
-            return xy.reshape(-1, 2) * scale
-        pts = np.concatenate([coords(points_a, recs["query"]), coords(points_b, recs["train"])], axis=1)
+        pts = np.concatenate([self._coords(points_a, recs["query"], localized, 0), self._coords(points_b, recs["train"], localized, 1)], axis=1)
         run = self.ctx.ransac_fundamental if model == "fundamental" else self.ctx.ransac_homography
         models, inlier = run(pts, None, iterations, threshold, seed, refine=refine)
         return recs, models[0], inlier
 
-    def refine_fundamental(self, points_a, points_b, recs, model, threshold: float = 3.0, rounds: int = 2):
+    def refine_fundamental(self, points_a, points_b, recs, model, threshold: float = 3.0, rounds: int = 2, localized=None):
         """The least-squares refit of the record verify(model="fundamental") returned, over its own inliers among `recs` (an
         extension; Context.refine_fundamental) -> (model, refined, inlier): at most `rounds` (0 .. 8) rounds of which `refined`
-        were accepted; the inlier count never decreases.  Coordinates as verify() forms them."""
+        were accepted; the inlier count never decreases.  Coordinates, and `localized`, as for verify()."""
         if "f" not in (getattr(getattr(model, "dtype", None), "names", None) or ()):
             raise ValueError("refine_fundamental: model must be a record as verify(model=\"fundamental\") returns it")
-        scale = np.float32(0.5 if self.subpixel else 1.0)
-
-        def coords(points, which):
-            xy = np.array([[points[i].loc[0] << points[i].octave, points[i].loc[1] << points[i].octave] for i in which], np.float32)
-            return xy.reshape(-1, 2) * scale
-        pts = np.concatenate([coords(points_a, recs["query"]), coords(points_b, recs["train"])], axis=1)
+        pts = np.concatenate([self._coords(points_a, recs["query"], localized, 0), self._coords(points_b, recs["train"], localized, 1)], axis=1)
         models, refined, inlier = self.ctx.refine_fundamental(pts, None, np.asarray(model).reshape(1), threshold, rounds)
         return models[0], int(refined[0]), inlier
 
-    def match_guided(self, points_a, points_b, model, threshold: float = 3.0, ratio: float = 0.8, cross_check: bool = False):
+    def match_guided(self, points_a, points_b, model, threshold: float = 3.0, ratio: float = 0.8, cross_check: bool = False, localized=None):
         """match() again under the model verify() returned (an extension): a point of b competes for a point of a only when it
         lies within `threshold` pixels of the model - of the transferred point (a homography record) or of the epipolar line (a
-        fundamental record).  Coordinates as verify() forms them.  A model that is none (all zeros) gives no records."""
+        fundamental record).  Coordinates, and `localized`, as for verify().  A model that is none (all zeros) gives no records."""
         names = getattr(getattr(model, "dtype", None), "names", None) or ()
         if "h" not in names and "f" not in names:
             raise ValueError("match_guided: model must be a record as verify() returns it")
         kind = "homography" if "h" in names else "fundamental"
-        scale = np.float32(0.5 if self.subpixel else 1.0)
 
-        def rows(points):
+        def rows(points, side):
             d = np.zeros((len(points), 128), np.float32)
             kp = np.zeros(len(points), _lib.KEYPOINT_DTYPE)
-            xy = np.zeros((len(points), 2), np.float32)
             for i, p in enumerate(points):
-                xy[i] = (p.loc[0] << p.octave, p.loc[1] << p.octave)
                 if len(p.descriptors) == 128:
                     d[i] = p.descriptors
                     kp["has_descriptor"][i] = 1
-            return d, kp, xy * scale
-        qa, ka, xa = rows(points_a)
-        qb, kb, xb = rows(points_b)
+            return d, kp, self._coords(points, range(len(points)), localized, side)
+        qa, ka, xa = rows(points_a, 0)
+        qb, kb, xb = rows(points_b, 1)
         return self.ctx.match_guided(qa, qb, xa, xb, np.asarray(model["h" if kind == "homography" else "f"], np.float32), kind, threshold,
                                      ratio, cross_check, ka, kb)

@@ -56,6 +56,34 @@ def synth_batch(n: int, width: int, height: int, first_seed: int = 1) -> np.ndar
     return np.stack([synth_frame(width, height, first_seed + i) for i in range(n)])
 
 
+def warp_frame(img: np.ndarray, H) -> np.ndarray:
+    """`img` seen through the homography H (3 x 3, source to destination, x right and y down): destination pixel p takes the
+    bilinear sample of img at H^-1 p, rounded to 8-bit values; outside the source it is the border pixel.  Same size as img."""
+    h, w = img.shape
+    Hi = np.linalg.inv(np.asarray(H, np.float64))
+    y, x = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+    d = Hi[2, 0] * x + Hi[2, 1] * y + Hi[2, 2]
+    sx = np.clip((Hi[0, 0] * x + Hi[0, 1] * y + Hi[0, 2]) / d, 0, w - 1)
+    sy = np.clip((Hi[1, 0] * x + Hi[1, 1] * y + Hi[1, 2]) / d, 0, h - 1)
+    x0, y0 = np.minimum(sx.astype(np.int64), w - 2), np.minimum(sy.astype(np.int64), h - 2)
+    fx, fy = sx - x0, sy - y0
+    src = img.astype(np.float64)
+    out = ((src[y0, x0] * (1 - fx) + src[y0, x0 + 1] * fx) * (1 - fy) + (src[y0 + 1, x0] * (1 - fx) + src[y0 + 1, x0 + 1] * fx) * fy)
+    return np.rint(out).astype(np.float32)
+
+
+def quadratic_stack(L: int, w: int, h: int, centre, v, a=(0.5, 0.25, 1.0), c: float = 100.0) -> np.ndarray:
+    """A known-answer input of Context.localize_points: the stack [L, h, w] of d(p) = c - 0.5 * sum a_k (p_k - centre_k - v_k)^2
+    over p = (x, y, i).  With a_k powers of two and v_k dyadic every sample, the gradient, the Hessian and the determinant are
+    exact in float32 / float64, and the offset found at `centre` is exactly v."""
+    i, y, x = np.meshgrid(np.arange(L, dtype=np.float64), np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+    q = sum(ak * (p - ck - vk) ** 2 for ak, p, ck, vk in zip(a, (x, y, i), centre, v))
+    d = (c - 0.5 * q).astype(np.float32)
+    if not (d.astype(np.float64) == c - 0.5 * q).all():
+        raise ValueError("quadratic_stack: the samples are not exact in float32")
+    return d
+
+
 def blob_frame(width: int, height: int, seed: int, pitch: int = 11, sigma: float = 3.0) -> np.ndarray:
     """A dense lattice of Gaussian-ish blobs (one per pitch x pitch cell, amplitude 128..255 and a -1/0/+1 px
     offset drawn from the seeded stream), 8-bit-valued float32.  Roughly every second extremum candidate of such a

@@ -29,6 +29,15 @@ APPENDS its lines to --out.
     python tools/ransac_bench.py --refine-arm [--reps 20] [--out profiles/ransac_bench.txt]
     python tools/ransac_bench.py --fundamental-arm [--reps 20] [--out profiles/ransac_bench.txt]
     python tools/ransac_bench.py --fund-refit-arm [--reps 20] [--out profiles/ransac_bench.txt]
+
+The localisation arm (--localize-arm) times sift_hip_result_localize on the bench batch - host time around the call, which
+returns when the records are in place in device memory: the upload of the images' row offsets, the one launch and the wait; it
+is the CALL, not the kernel alone - and compares its records bit for bit with the host loop on two images.  Then a frame and a
+copy of itself warped by a known non-integer homography (sift_amd/synthetic.py: warp_frame) go through verify_images with
+refine 2, with and without localisation: inlier counts and the refit's error against the true homography, in pixels, over the
+frame's corners and over the inliers' query points.  Recorded, not asserted.  It writes --out anew.
+
+    python tools/ransac_bench.py --localize-arm [--reps 20] [--out profiles/localize_bench.txt]
 """
 import argparse
 import json
@@ -61,6 +70,9 @@ def main():
     ap.add_argument("--fund-refit-arm", action="store_true",
                     help="only the refit arm of F: sift_hip_ransac_fundamental alone against the same call followed by "
                          "sift_hip_refine_fundamental at 8 rounds, appended to --out")
+    ap.add_argument("--localize-arm", action="store_true",
+                    help="only the localisation arm: sift_hip_result_localize on the bench batch, and verification of a warped copy "
+                         "with and without it; written to --out")
     args = ap.parse_args()
 
     import torch
@@ -214,6 +226,50 @@ def main():
     cnt = ctx.counts()
     row0 = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
     kp, _ = ctx.results()
+
+    if args.localize_arm:
+        import localize_ref
+        from sift_amd.synthetic import synth_frame, warp_frame
+        total = int(cnt.sum())
+        dev = torch.zeros(max(total, 1) * 32, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        for _ in range(args.warmup):
+            ctx.localize(5, False, dev)
+        call = timed(lambda: ctx.localize(5, False, dev), args.reps)
+        got = np.frombuffer(dev.cpu().numpy()[:total * 32].tobytes(), _lib.LOCALIZED_DTYPE)
+        want = localize_ref.batch_host(ctx, 3, False, (0, n - 1))   # the host loop over the levels read back, two images
+        ok = all(got[row0[img]:row0[img + 1]].tobytes() == want[row0[img]:row0[img + 1]].tobytes() for img in (0, n - 1))
+        emit({"case": f"localisation arm: sift_hip_result_localize on the {n}-frame 1920 x 1080 bench batch (3 DoGs, 4 octaves), records to device memory",
+              "keypoints": total, "max_moves": 5, "call": call, "ns_per_keypoint_median": round(call["median_ms"] * 1e6 / max(total, 1), 2),
+              "status_counts": np.bincount(got["status"], minlength=5).tolist(), "moved": int((got["moves"] > 0).sum()),
+              "bitwise_equal_to_host_loop_on_two_images": bool(ok), "kernel_time_alone": "not measured"})
+        Ht = np.array([[1.02 * np.cos(0.05), -1.02 * np.sin(0.05), 7.3], [1.02 * np.sin(0.05), 1.02 * np.cos(0.05), -4.6], [1.5e-5, -1.0e-5, 1.0]])
+        a = synth_frame(1024, 768, 1)
+        pair = np.stack([a, warp_frame(a, Ht)])
+        corners = np.array([[0, 0, 1], [1023, 0, 1], [0, 767, 1], [1023, 767, 1]], np.float64)
+
+        def px_error(h, q):
+            est, true = (np.asarray(h, np.float64).reshape(3, 3) @ q.T).T, (Ht @ q.T).T
+            return np.hypot(est[:, 0] / est[:, 2] - true[:, 0] / true[:, 2], est[:, 1] / est[:, 2] - true[:, 1] / true[:, 2])
+        for dogs in (3,):   # (with five DoGs a keypoint of this frame lands in the level whose dead 16 x 16 blur throws, sift.cpp:184)
+            ctx.calculate_batch(pair, _lib.Params(dogs, 4, 1.6, K_SQRT2, 0))
+            k2, _ = ctx.results()
+            loc = ctx.localize()
+            plain = np.stack([k2["x"].astype(np.int64) << k2["octave"], k2["y"].astype(np.int64) << k2["octave"]], axis=1).astype(np.float64)
+            for t in (3.0, 1.0):
+                for localized in (False, True):
+                    rec, _, models, inl = ctx.verify_images([(0, 1)], 0.8, False, its, t, 0, 2, "homography", localized=localized)
+                    q = (np.stack([loc["x"], loc["y"]], axis=1).astype(np.float64) if localized else plain)[rec["query"][inl != 0]]
+                    q = np.concatenate([q, np.ones((q.shape[0], 1))], axis=1)
+                    emit({"case": "localisation arm: a 1024 x 768 frame against its copy warped by a known homography, verify_images refine 2",
+                          "dogs_per_epoch": dogs, "threshold_px": t, "localized": localized, "keypoints": ctx.counts().tolist(),
+                          "status_ok_share": round(float((loc["status"] == 0).mean()), 3), "matches": int(rec.size),
+                          "inliers": int(models["inliers"][0]), "refined_rounds": int(models["refined"][0]),
+                          "corner_error_px_max": round(float(px_error(models["h"][0], corners).max()), 4) if models["iteration"][0] >= 0 else None,
+                          "inlier_reprojection_error_px_mean": round(float(px_error(models["h"][0], q).mean()), 4) if q.shape[0] else None})
+        ctx.close()
+        finish("w", ["# tools/ransac_bench.py --localize-arm: JSON lines.  Times are host times around calls that return when the result is in place.\n"])
+        return
 
     # ---- (a): two 1080p frames' match list ----
     rec, counts = ctx.match_images([(0, 1)], 0.8, False)
