@@ -3,7 +3,8 @@
 // a point of b competing for a point of a only within `threshold` pixels of the verified model (include/sift/match.hpp;
 // extensions, the reference has none of them).  guided.txt has the format of matches.txt; with no model it is empty.
 //   g++ -std=c++17 -pthread -Iinclude examples/sift_guided.cpp -Lsift_amd/lib -lsift_hip -Wl,-rpath,$PWD/sift_amd/lib -o sift_guided
-//   ./sift_guided a.pgm b.pgm [model=homography|fundamental] [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [guidedRatio=ratio]
+//   ./sift_guided a.pgm b.pgm [model=homography|fundamental] [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [guidedRatio=ratio] [u8]
+// A trailing `u8`, after any number of the optional arguments: guided.txt comes from the 8-bit guided matcher - match_guided(..., quantized = true).
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -37,9 +38,11 @@ static void write_matches(const char* path, const std::vector<sift::Match>& matc
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::cerr << "usage: " << argv[0]
-                  << " a.{pgm,ppm,png,jpg} b.{...} [homography|fundamental] [octaves] [dogsPerEpoch] [ratio] [crossCheck] [iterations] [threshold] [seed] [guidedRatio]\n";
+                  << " a.{pgm,ppm,png,jpg} b.{...} [homography|fundamental] [octaves] [dogsPerEpoch] [ratio] [crossCheck] [iterations] [threshold] [seed] [guidedRatio] [u8]\n";
         return 1;
     }
+    const bool u8 = argc > 3 && std::string(argv[argc - 1]) == "u8";
+    if (u8) --argc;
     const std::string model_name = argc > 3 ? argv[3] : "homography";
     const u16_t octaves = argc > 4 ? (u16_t)std::atoi(argv[4]) : 4;
     const u16_t dogsPerEpoch = argc > 5 ? (u16_t)std::atoi(argv[5]) : 3;
@@ -66,12 +69,12 @@ int main(int argc, char** argv) {
             const sift::Fundamental model = matcher.verify_fundamental(a, b, matches, iterations, threshold, seed, false);
             write_matches("inliers.txt", matches, &model.inlier);
             inliers = model.inliers;
-            guided = matcher.match_guided(a, b, model, threshold, guidedRatio, crossCheck, false);
+            guided = matcher.match_guided(a, b, model, threshold, guidedRatio, crossCheck, false, u8);
         } else {
             const sift::Homography model = matcher.verify(a, b, matches, iterations, threshold, seed, false, 0);
             write_matches("inliers.txt", matches, &model.inlier);
             inliers = model.inliers;
-            guided = matcher.match_guided(a, b, model, threshold, guidedRatio, crossCheck, false);
+            guided = matcher.match_guided(a, b, model, threshold, guidedRatio, crossCheck, false, u8);
         }
         write_matches("guided.txt", guided, nullptr);
         std::cout << a.size() << " and " << b.size() << " interest points, " << matches.size() << " matches -> matches.txt, " << inliers

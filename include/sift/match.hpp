@@ -78,14 +78,17 @@ public:
     // is the best query point seen from a train point (crossCheck).  Repeated structure, which the plain ratio test drops, comes
     // back.  Coordinates as verify() forms them: loc * 2^octave, halved when the points come from a subpixel run.  A model that
     // is none (iteration -1: all zeros) gives no matches.  Throws std::invalid_argument for a threshold that is not finite and
-    // positive and for what match() rejects.
+    // positive and for what match() rejects.  quantized: as for match() - the descriptors are quantised to 8 bits on the GPU and the
+    // guided matcher runs on the i8 matrix cores (include/sift_hip.h, "guided matching on 8-bit descriptors").
     std::vector<Match> match_guided(const std::vector<InterestPoint>& query, const std::vector<InterestPoint>& train, const Homography& model,
-                                    f32_t threshold = 3.0f, f32_t ratio = 0.8f, bool crossCheck = false, bool subpixel = false) {
-        return guided(query, train, SIFT_HIP_GUIDE_HOMOGRAPHY, model.h, threshold, ratio, crossCheck, subpixel);
+                                    f32_t threshold = 3.0f, f32_t ratio = 0.8f, bool crossCheck = false, bool subpixel = false,
+                                    bool quantized = false) {
+        return guided(query, train, SIFT_HIP_GUIDE_HOMOGRAPHY, model.h, threshold, ratio, crossCheck, subpixel, quantized);
     }
     std::vector<Match> match_guided(const std::vector<InterestPoint>& query, const std::vector<InterestPoint>& train, const Fundamental& model,
-                                    f32_t threshold = 3.0f, f32_t ratio = 0.8f, bool crossCheck = false, bool subpixel = false) {
-        return guided(query, train, SIFT_HIP_GUIDE_FUNDAMENTAL, model.f, threshold, ratio, crossCheck, subpixel);
+                                    f32_t threshold = 3.0f, f32_t ratio = 0.8f, bool crossCheck = false, bool subpixel = false,
+                                    bool quantized = false) {
+        return guided(query, train, SIFT_HIP_GUIDE_FUNDAMENTAL, model.f, threshold, ratio, crossCheck, subpixel, quantized);
     }
 
     // The geometric check of a match list (include/sift_hip.h, "geometric verification"): the best four-point homography
@@ -217,7 +220,7 @@ private:
         return out;
     }
     std::vector<Match> guided(const std::vector<InterestPoint>& query, const std::vector<InterestPoint>& train, unsigned kind, const f32_t (&m)[9],
-                              f32_t threshold, f32_t ratio, bool crossCheck, bool subpixel) {
+                              f32_t threshold, f32_t ratio, bool crossCheck, bool subpixel, bool quantized) {
         const size_t nq = query.size(), nt = train.size();
         rows(query, train);
         const f32_t scale = subpixel ? 0.5f : 1.0f;
@@ -237,8 +240,17 @@ private:
         int32_t count = 0;
         int64_t total = 0;
         char err[512] = "";
-        const int rc = sift_hip_match_guided(_ctx, _desc.data(), _kp.data(), _xy.data(), 2, offsets, 1, &pq, &pt, &prm, &guide, m, _recs.data(), &count,
-                                             &total, err, sizeof(err));
+        int rc;
+        if (quantized) {   // the bytes of sift_hip_quantize through the byte call
+            _desc8.resize(_desc.size());
+            rc = sift_hip_quantize(_ctx, _desc.data(), (int64_t)(nq + nt), _desc8.data(), err, sizeof(err));
+            if (rc == SIFT_HIP_OK)
+                rc = sift_hip_match_guided_u8(_ctx, _desc8.data(), _kp.data(), _xy.data(), 2, offsets, 1, &pq, &pt, &prm, &guide, m, _recs.data(),
+                                              &count, &total, err, sizeof(err));
+        } else {
+            rc = sift_hip_match_guided(_ctx, _desc.data(), _kp.data(), _xy.data(), 2, offsets, 1, &pq, &pt, &prm, &guide, m, _recs.data(), &count,
+                                       &total, err, sizeof(err));
+        }
         if (rc == SIFT_HIP_EINVAL) throw std::invalid_argument(err);
         if (rc != SIFT_HIP_OK) throw std::runtime_error(err);
         return records((size_t)total);
@@ -256,6 +268,7 @@ private:
 
     sift_hip_ctx* _ctx = nullptr;
     std::vector<float> _desc;              // both lists' rows back to back, kept between calls
+    std::vector<uint8_t> _desc8;           // guided matching with quantized: the rows as bytes
     std::vector<sift_hip_keypoint> _kp;
     std::vector<sift_hip_match_rec> _recs;
     std::vector<float> _pts;

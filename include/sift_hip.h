@@ -456,9 +456,9 @@ int sift_hip_result_match_guided(sift_hip_ctx* ctx, int n_pairs, const int32_t* 
  *
  * sift_hip_match_params.quantized = 1 in sift_hip_match, sift_hip_result_match, sift_hip_result_verify and
  * sift_hip_result_verify_fundamental: the float rows are quantised on the device into scratch memory kept with the context and
- * the integer matcher runs - bit for bit sift_hip_quantize followed by sift_hip_match_u8.  In the three guided calls
- * quantized = 1 is SIFT_HIP_EINVAL: guided matching takes float rows only.  The two _u8 calls below take bytes whatever the
- * flag says (0 or 1). */
+ * the integer matcher runs - bit for bit sift_hip_quantize followed by sift_hip_match_u8.  In the three float guided calls
+ * quantized = 1 is SIFT_HIP_EINVAL: guided matching over bytes is the three _guided_u8 calls ("guided matching on 8-bit
+ * descriptors" below).  The two _u8 calls below take bytes whatever the flag says (0 or 1). */
 /* rows x 128 floats -> rows x 128 bytes; each side may be host or device memory; zero rows is legal. */
 int sift_hip_quantize(sift_hip_ctx* ctx, const float* desc, int64_t rows, uint8_t* out, char* err, int errlen);
 /* The descriptors of the last batch, quantised on the GPU: sift_hip_result_total() * 128 bytes to host or device memory,
@@ -470,6 +470,35 @@ int sift_hip_knn2_u8(sift_hip_ctx* ctx, const uint8_t* desc, const sift_hip_keyp
 int sift_hip_match_u8(sift_hip_ctx* ctx, const uint8_t* desc, const sift_hip_keypoint* kp, int n_sets, const int64_t* offsets,
                       int n_pairs, const int32_t* pair_q, const int32_t* pair_t, const sift_hip_match_params* params,
                       sift_hip_match_rec* recs, int32_t* counts, int64_t* total, char* err, int errlen);
+
+/* ---- guided matching on 8-bit descriptors (an extension) ---------------------------------------------------
+ * "Guided matching" over the byte rows and the integer distance of "8-bit descriptors and integer matching"; nothing else is new.
+ * A candidate (d2, j) for query row i is d2 = sum (a[k] - b[k])^2, delivered as (float)d2; it takes part when both rows are valid
+ * AND j is admissible for i under the pair's model - ransac_inlier or ransac_fund_inlier with thr2 = threshold * threshold, as
+ * "guided matching" calls them; the cross-check uses the same model in the same direction; the all-zero model admits nothing; a
+ * NaN or infinite coordinate is admissible for nothing.  Candidates are ordered by (d2, j), a missing entry is -1 / +inf, the
+ * float ratio test, the cross-check, sets, pairs, offsets and the memory rules are those of the existing calls; one launch of each
+ * kernel per call; the result does not depend on tiles, splits or the launch shape.  A plain host loop
+ * (hostmath_match_knn2_guided_u8) checks every bit.  Inside the tile kernel each predicate is evaluated in parts - what depends
+ * on one point alone once per row, the rest per (query, train) - by the functions next to the predicates in ransac_math.h and
+ * ransac_fund_math.h, which perform the predicates' operations in the predicates' order (hostmath_guided_admissible_split).
+ *
+ * match_params->quantized may be 0 or 1 in these calls, and they take bytes either way; above 1 is SIFT_HIP_EINVAL.  Byte rows in
+ * device memory must be aligned to 16 bytes.  Everything the guided calls and the _u8 calls reject is rejected here.
+ * sift_hip_result_match_guided_u8 runs over the last batch: the float rows are quantised on the device into the context's byte
+ * scratch in the pass that forms their norms, and the coordinates are those of sift_hip_result_match_guided (the localised ones
+ * after sift_hip_result_localize with use = 1) - bit for bit sift_hip_result_copy_u8 followed by sift_hip_match_guided_u8 on those
+ * coordinates. */
+int sift_hip_knn2_guided_u8(sift_hip_ctx* ctx, const uint8_t* desc, const sift_hip_keypoint* kp, const float* xy, int n_sets,
+                            const int64_t* offsets, int n_pairs, const int32_t* pair_q, const int32_t* pair_t,
+                            const sift_hip_guide_params* guide, const float* models, int32_t* idx, float* dist2, char* err, int errlen);
+int sift_hip_match_guided_u8(sift_hip_ctx* ctx, const uint8_t* desc, const sift_hip_keypoint* kp, const float* xy, int n_sets,
+                             const int64_t* offsets, int n_pairs, const int32_t* pair_q, const int32_t* pair_t,
+                             const sift_hip_match_params* match_params, const sift_hip_guide_params* guide, const float* models,
+                             sift_hip_match_rec* recs, int32_t* counts, int64_t* total, char* err, int errlen);
+int sift_hip_result_match_guided_u8(sift_hip_ctx* ctx, int n_pairs, const int32_t* pair_q, const int32_t* pair_t,
+                                    const sift_hip_match_params* match_params, const sift_hip_guide_params* guide, const float* models,
+                                    sift_hip_match_rec* recs, int32_t* counts, int64_t* total, char* err, int errlen);
 
 /* ---- sub-pixel localisation (an extension) -----------------------------------------------------------------
  * Every coordinate above is (float)(x << octave): a keypoint of octave 2 sits on a 4-pixel grid of the image.  The reference

@@ -41,6 +41,7 @@ SYMBOLS = [
     "sift_hip_refine_fundamental", "sift_hip_result_refine_fundamental",
     "sift_hip_knn2_guided", "sift_hip_match_guided", "sift_hip_result_match_guided",
     "sift_hip_quantize", "sift_hip_result_copy_u8", "sift_hip_knn2_u8", "sift_hip_match_u8",
+    "sift_hip_knn2_guided_u8", "sift_hip_match_guided_u8", "sift_hip_result_match_guided_u8",
     "sift_hip_result_localize", "sift_hip_localize_points",
 ]
 
@@ -230,6 +231,9 @@ def load():
     L.sift_hip_result_copy_u8.argtypes = [vp, vp]
     L.sift_hip_knn2_u8.argtypes = L.sift_hip_knn2.argtypes
     L.sift_hip_match_u8.argtypes = L.sift_hip_match.argtypes
+    L.sift_hip_knn2_guided_u8.argtypes = L.sift_hip_knn2_guided.argtypes
+    L.sift_hip_match_guided_u8.argtypes = L.sift_hip_match_guided.argtypes
+    L.sift_hip_result_match_guided_u8.argtypes = L.sift_hip_result_match_guided.argtypes
     # out: host or device memory
     L.sift_hip_result_localize.argtypes = [vp, ci, ci, vp, cs, ci]
     L.sift_hip_localize_points.argtypes = [vp, fp, ci, ci, ci, u16p, u16p, u16p, ci, ci, vp, cs, ci]

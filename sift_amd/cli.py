@@ -150,7 +150,9 @@ def main(argv=None) -> int:
     ap.add_argument("--guided", action="store_true",
                     help="with --verify: match again under the winning model (a point competes only within --threshold pixels of it); "
                          "the matches go to guided.txt")
-    ap.add_argument("--guided-ratio", type=float, default=None, help="ratio test of --guided (default: --ratio)")
+    ap.add_argument("--guided-u8", action="store_true",
+                    help="with --verify: --guided by the 8-bit guided matcher (descriptors quantised to 8 bits, integer distances)")
+    ap.add_argument("--guided-ratio", type=float, default=None, help="ratio test of --guided / --guided-u8 (default: --ratio)")
     ap.add_argument("--u8", action="store_true",
                     help="with --match: quantise the descriptors to 8 bits on the GPU and match by the integer distance (the distances "
                          "in matches.txt are integers)")
@@ -165,8 +167,12 @@ def main(argv=None) -> int:
         ap.error("--u8 needs --match")
     if args.u8 and args.guided:
         ap.error("--u8 cannot be combined with --guided: guided matching takes float descriptors only")
-    if args.guided_ratio is not None and not args.guided:
-        ap.error("--guided-ratio needs --guided")
+    if args.guided_u8 and not args.verify:
+        ap.error("--guided-u8 needs --verify")
+    if args.guided_u8 and args.guided:
+        ap.error("--guided-u8 and --guided both write guided.txt: give one")
+    if args.guided_ratio is not None and not (args.guided or args.guided_u8):
+        ap.error("--guided-ratio needs --guided or --guided-u8")
     if args.model != "homography" and not args.verify:
         ap.error("--model needs --verify")
     if args.refine and args.model == "fundamental":
@@ -224,9 +230,10 @@ def main(argv=None) -> int:
                 else:
                     for r in range(3):
                         print("H " + " ".join("%.9g" % float(v) for v in model["h"][3 * r:3 * r + 3]))
-                if args.guided:   # no winner: the all-zero model admits nothing, the file is empty
+                if args.guided or args.guided_u8:   # no winner: the all-zero model admits nothing, the file is empty
                     ratio = args.ratio if args.guided_ratio is None else args.guided_ratio
-                    guided = sift.match_guided(points, points2, model, args.threshold, ratio, args.cross_check, localized)
+                    guided = sift.match_guided(points, points2, model, args.threshold, ratio, args.cross_check, localized,
+                                               args.guided_u8)
                     write_matches("guided.txt", guided)
                     print(f"{len(guided)} guided matches -> guided.txt")
     except (PreconditionViolation, AssertionError, RuntimeError, OSError) as ex:  # main.cpp:90-92

@@ -191,6 +191,76 @@ void hostmath_match_knn2_u8(const uint8_t* q, const uint8_t* q_valid, long long 
         dist2[2 * i + 1] = i2 < 0 ? INFINITY : (float)d2;
     }
 }
+// Guided matching over byte rows (include/sift_hip.h, "guided matching on 8-bit descriptors"): hostmath_match_knn2_u8 with the
+// condition of hostmath_match_knn2_guided - the int32 distance, the UNSPLIT predicates, the same arguments and `reverse`.
+void hostmath_match_knn2_guided_u8(const uint8_t* q, const uint8_t* q_valid, const float* q_xy, long long nq, const uint8_t* t,
+                                   const uint8_t* t_valid, const float* t_xy, long long nt, int model, const float* m, float threshold, int reverse,
+                                   int32_t* idx, float* dist2) {
+    float mm[9];
+    for (int k = 0; k < 9; ++k) mm[k] = m[k];
+    const float thr2 = threshold * threshold;
+    const uint8_t* own = reverse ? t : q;
+    const uint8_t* other = reverse ? q : t;
+    const uint8_t* own_valid = reverse ? t_valid : q_valid;
+    const uint8_t* other_valid = reverse ? q_valid : t_valid;
+    const long long n_own = reverse ? nt : nq, n_other = reverse ? nq : nt;
+    for (long long i = 0; i < n_own; ++i) {
+        int32_t d1 = 0, d2 = 0, i1 = -1, i2 = -1;
+        if (!own_valid || own_valid[i]) {
+            for (long long j = 0; j < n_other; ++j) {
+                if (other_valid && !other_valid[j]) continue;
+                const long long qi = reverse ? j : i, tj = reverse ? i : j;
+                const bool adm = model == 1 ? sift_hip::ransac_fund_inlier(mm, q_xy[2 * qi], q_xy[2 * qi + 1], t_xy[2 * tj], t_xy[2 * tj + 1], thr2)
+                                            : sift_hip::ransac_inlier(mm, q_xy[2 * qi], q_xy[2 * qi + 1], t_xy[2 * tj], t_xy[2 * tj + 1], thr2);
+                if (!adm) continue;
+                int32_t d = 0;
+                for (int k = 0; k < 128; ++k) {
+                    const int32_t e = (int32_t)own[i * 128 + k] - (int32_t)other[j * 128 + k];
+                    d += e * e;
+                }
+                if (i1 < 0 || d < d1) {
+                    d2 = d1; i2 = i1; d1 = d; i1 = (int32_t)j;
+                } else if (i2 < 0 || d < d2) {
+                    d2 = d; i2 = (int32_t)j;
+                }
+            }
+        }
+        idx[2 * i] = i1; idx[2 * i + 1] = i2;
+        dist2[2 * i] = i1 < 0 ? INFINITY : (float)d1;
+        dist2[2 * i + 1] = i2 < 0 ? INFINITY : (float)d2;
+    }
+}
+// The nq x nt admissibility matrix through the predicates' split parts, composed as the guided 8-bit tile kernel composes them:
+// the part of the row that owns the loop once, the parts of the other side's rows once each, the tail per element.  reverse 0:
+// the query rows own the loop (a forward tile); reverse 1: the train rows do (a tile of the cross-check).  out[i * nt + j] either way.
+void hostmath_guided_admissible_split(int model, const float* m, float threshold, const float* q_xy, long long nq, const float* t_xy,
+                                      long long nt, int reverse, uint8_t* out) {
+    float mm[9];
+    for (int k = 0; k < 9; ++k) mm[k] = m[k];
+    const float thr2 = threshold * threshold;
+    auto query_part = [&](long long i, float (&p)[4]) {
+        if (model == 1) sift_hip::ransac_fund_inlier_query(mm, q_xy[2 * i], q_xy[2 * i + 1], thr2, p);
+        else sift_hip::ransac_inlier_query(mm, q_xy[2 * i], q_xy[2 * i + 1], thr2, p);
+    };
+    auto train_part = [&](long long j, float (&p)[4]) {
+        if (model == 1) sift_hip::ransac_fund_inlier_train(mm, t_xy[2 * j], t_xy[2 * j + 1], p);
+        else sift_hip::ransac_inlier_train(mm, t_xy[2 * j], t_xy[2 * j + 1], p);
+    };
+    const long long n_own = reverse ? nt : nq, n_other = reverse ? nq : nt;
+    float (*stage)[4] = new float[n_other > 0 ? n_other : 1][4];
+    for (long long j = 0; j < n_other; ++j) reverse ? query_part(j, stage[j]) : train_part(j, stage[j]);
+    for (long long i = 0; i < n_own; ++i) {
+        float mine[4];
+        reverse ? train_part(i, mine) : query_part(i, mine);
+        for (long long j = 0; j < n_other; ++j) {
+            const float (&qp)[4] = reverse ? stage[j] : mine;
+            const float (&tp)[4] = reverse ? mine : stage[j];
+            const bool ok = model == 1 ? sift_hip::ransac_fund_inlier_tail(qp, tp, thr2) : sift_hip::ransac_inlier_tail(qp, tp, thr2);
+            out[reverse ? j * nt + i : i * nt + j] = ok ? 1 : 0;
+        }
+    }
+    delete[] stage;
+}
 // RANSAC homography as ransac_math.h defines it, in plain loops: what sift_hip_ransac_homography must reproduce bit for bit.
 void hostmath_ransac_draw(uint32_t seed, uint32_t set, uint32_t iteration, uint32_t m, uint32_t* idx) {
     uint32_t d[4];

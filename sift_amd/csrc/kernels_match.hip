@@ -18,7 +18,7 @@
 #include <algorithm>
 
 #include "match_kernels.h"
-#include "ransac_fund_math.h"   // ransac_inlier, ransac_fund_inlier: the guided instantiations' admissibility test
+#include "match_guides.h"   // NoGuide, HomographyGuide, FundamentalGuide: the guided instantiations' admissibility test
 
 namespace sift_hip {
 
@@ -49,25 +49,6 @@ __device__ __forceinline__ void store_row4(float* row, int c4, f4v v) {
     *reinterpret_cast<f2v*>(row + 2 * c4) = e;
     *reinterpret_cast<f2v*>(row + 64 + 2 * c4) = o;
 }
-
-// The guide of a tile kernel instantiation (include/sift_hip.h, "guided matching"): none, or one of the two verification
-// predicates, called with the arguments the RANSAC kernels give them.
-struct NoGuide {
-    static constexpr bool kOn = false;
-    static __device__ __forceinline__ bool admissible(const float (&)[9], float, float, float, float, float) { return true; }
-};
-struct HomographyGuide {
-    static constexpr bool kOn = true;
-    static __device__ __forceinline__ bool admissible(const float (&m)[9], float qx, float qy, float tx, float ty, float thr2) {
-        return ransac_inlier(m, qx, qy, tx, ty, thr2);
-    }
-};
-struct FundamentalGuide {
-    static constexpr bool kOn = true;
-    static __device__ __forceinline__ bool admissible(const float (&m)[9], float qx, float qy, float tx, float ty, float thr2) {
-        return ransac_fund_inlier(m, qx, qy, tx, ty, thr2);
-    }
-};
 
 }  // namespace
 

@@ -14,6 +14,9 @@
 // Stride 144 bytes = 9 slots of 16 bytes: a ds_read_b128 is served in four groups of 16 lanes, each group holding every residue
 // of c mod 16 once (lanes 0-3, 12-15, 20-27 / 4-11, 16-19, 28-31 of a half), and 9 c mod 16 is a bijection on those residues (9 is
 // odd) - 16 lanes, 16 different slots, the 64 banks once.  LDS: 2 * 64 * 144 + 2 * 64 * 4 + 2 * 64 = 19 072 bytes.
+#include <type_traits>
+
+#include "match_guides.h"
 #include "match_kernels.h"
 
 namespace sift_hip {
@@ -106,12 +109,29 @@ __global__ __launch_bounds__(256) void match_norm_u8_kernel(const float* __restr
     }
 }
 
+// Guide::kOn ("guided matching on 8-bit descriptors"): a candidate also has to be admissible under its pair's model.  Here a
+// wave-stage is 8 matrix instructions, not 128: 32 whole predicates per lane and stage would cost several times the rest, so the
+// kernel is built around a cheap predicate that switches the products off.
+//   parts     each predicate is split by point (ransac_math.h, ransac_fund_math.h).  The part of the lane's own row is formed once
+//             per tile and stays in four registers.  The parts of the stage's rows are formed once per row by the 64 threads that
+//             fetch the stage's norms and flags, and travel through LDS with them, one plane of 64 floats per component: the lane
+//             reads a component of 4 consecutive rows in one 16-byte read, the same address for the 32 lanes of a half-wave (a
+//             broadcast, no bank conflict), and only the planes its direction uses.  A forward tile carries the train part; a tile
+//             of the cross-check (pair_dir & 1), where the lane's row is the predicate's train row, carries the query part.  Only
+//             the tail runs per element.  A row that is invalid or past the range carries NaNs: admissible for nothing.
+//   first     the lane forms its 32 admissibility bits BEFORE the products.  A 32-row half of the stage in which no lane of the
+//             wave has a bit is skipped whole: its four operand reads, four matrix instructions and 16-element epilogue.  Under a
+//             verified homography at a few pixels that is nearly every half; under a fundamental matrix it is few - then the
+//             epilogue's ballot asks for an admissible candidate within the lane's second best, as the f32 kernel's does.
+// The unguided instantiation compiles to the code it was before the guide existed (DESIGN.md 3h has the comparison).
+template <class Guide>
 __global__ __launch_bounds__(256) void match_tile_u8_kernel(const uint8_t* __restrict__ desc, const int32_t* __restrict__ norm,
                                                             const uint8_t* __restrict__ valid, const MatchTile* __restrict__ tiles,
-                                                            MatchTop2* __restrict__ part) {
+                                                            MatchTop2* __restrict__ part, MatchGuideArgs ga) {
     __shared__ __attribute__((aligned(16))) unsigned char st[2][kMatchT * kRowStrideU8];
     __shared__ __attribute__((aligned(16))) int stn[2][kMatchT];
     __shared__ __attribute__((aligned(16))) unsigned char stv[2][kMatchT];
+    __shared__ __attribute__((aligned(16))) float stp[2][Guide::kOn ? 4 * kMatchT : 4];   // component k of stage row r at [64 k + r]
 
     struct { int q_row0, q_rows, t_set0, t_lo, t_hi; } tl;   // wave-uniform: scalar registers
     tl.q_row0 = tiles[blockIdx.x].q_row0; tl.q_rows = tiles[blockIdx.x].q_rows; tl.t_set0 = tiles[blockIdx.x].t_set0;
@@ -131,10 +151,34 @@ __global__ __launch_bounds__(256) void match_tile_u8_kernel(const uint8_t* __res
         for (int s = 0; s < 4; ++s) b[s] = qrow[2 * s + h] ^ kSignFlip;
         nq = norm[tl.q_row0 + my_q];
     }
+    float gm[9] = {};        // the tile's model (scalar registers)
+    bool swapped = false;    // a tile of the cross-check: the lane's row is the train row of the predicate
+    float own[4];            // the lane's own part
+    // the part of row `row` that a stage (stage_side) or a lane carries in this tile; NaNs when the row takes no part
+    auto part_of = [&](bool live, size_t row, bool stage_side, float (&p)[4]) {
+        float x = 0.0f, y = 0.0f;
+        if (live) {
+            x = ga.xy[2 * row];
+            y = ga.xy[2 * row + 1];
+        }
+        if (swapped == stage_side) Guide::query_part(gm, x, y, ga.thr2, p);
+        else Guide::train_part(gm, x, y, p);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) p[k] = live ? p[k] : __builtin_nanf("");
+    };
+    if constexpr (Guide::kOn) {
+        const int pd = tiles[blockIdx.x].pair_dir;
+        swapped = (pd & 1) != 0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) gm[k] = ga.models[9 * (size_t)(pd >> 1) + k];
+        const bool live = my_q < tl.q_rows && valid[tl.q_row0 + my_q] != 0;
+        part_of(live, (size_t)(tl.q_row0 + my_q), false, own);
+    }
 
     const int n_stages = (tl.t_hi - tl.t_lo + kMatchT - 1) / kMatchT;
     i4v pre[2];            // the next stage's rows on their way from memory: fetched before this stage's products, stored after
     int pre_n = 0, pre_v = 0;
+    float pre_p[4];
     auto fetch = [&](int stage) {
         const int t0 = tl.t_lo + stage * kMatchT;
 #pragma unroll
@@ -147,6 +191,7 @@ __global__ __launch_bounds__(256) void match_tile_u8_kernel(const uint8_t* __res
             const bool in = t0 + tid < tl.t_hi;      // rows past the range are masked by index, like invalid ones
             pre_n = in ? norm[tl.t_set0 + t0 + tid] : 0;
             pre_v = in ? (int)valid[tl.t_set0 + t0 + tid] : 0;
+            if constexpr (Guide::kOn) part_of(pre_v != 0, (size_t)(tl.t_set0 + t0 + tid), true, pre_p);
         }
     };
     auto stash = [&](int buf) {
@@ -158,6 +203,10 @@ __global__ __launch_bounds__(256) void match_tile_u8_kernel(const uint8_t* __res
         if (tid < kMatchT) {
             stn[buf][tid] = pre_n;
             stv[buf][tid] = (unsigned char)pre_v;
+            if constexpr (Guide::kOn) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) stp[buf][kMatchT * k + tid] = pre_p[k];
+            }
         }
     };
 
@@ -177,44 +226,102 @@ __global__ __launch_bounds__(256) void match_tile_u8_kernel(const uint8_t* __res
 
         const unsigned char* t0row = &st[buf][c * kRowStrideU8 + 16 * h];
         const unsigned char* t1row = t0row + 32 * kRowStrideU8;
-        i4v a0[4], a1[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            a0[s] = *reinterpret_cast<const i4v*>(t0row + 32 * s);
-            a1[s] = *reinterpret_cast<const i4v*>(t1row + 32 * s);
-        }
-        // the norms and valid flags of this lane's 32 train rows (4 consecutive rows per read), on their way during the products
-        i4v tn[8];
-        unsigned tv[8];
-#pragma unroll
-        for (int g = 0; g < 8; ++g) {
-            const int tr0 = (g >> 2) * 32 + 8 * (g & 3) + 4 * h;
-            tn[g] = *reinterpret_cast<const i4v*>(&stn[buf][tr0]);
-            tv[g] = *reinterpret_cast<const unsigned*>(&stv[buf][tr0]);
-        }
-        i16v acc0, acc1;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc0[r] = 0; acc1[r] = 0; }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {   // k = 32 s .. 32 s + 31 into the same accumulators
-            acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0[s], b[s], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1[s], b[s], acc1, 0, 0, 0);
-        }
-        // result element r of lane (c, h): train row (r & 3) + 8 (r >> 2) + 4 h of the half, query row c of the wave's 32.
-        // Once a few hundred rows have been seen nearly every candidate is farther than the lane's second best: the wave
-        // forms n'(b) - 2 dot' and leaves the rest (masks, the order) to the few elements where some lane is not beyond it.
         const int jbase = tl.t_lo + stage * kMatchT;
+        if constexpr (Guide::kOn) {
+            // bit 16 half + r: the stage row of result element r of that half is admissible for / by the lane's row
+            unsigned adm = 0u;
+            auto form_bits = [&](auto cross) {
+                constexpr bool kCross = decltype(cross)::value;
+                constexpr int kN = kCross ? Guide::kQueryN : Guide::kTrainN;   // the planes this direction's stage part uses
 #pragma unroll
-        for (int half = 0; half < 2; ++half) {
+                for (int g = 0; g < 8; ++g) {
+                    const int tr0 = (g >> 2) * 32 + 8 * (g & 3) + 4 * h;
+                    f4v comp[4];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int tr = half * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                const int dot = half ? acc1[r] : acc0[r];
-                const int u = tn[half * 4 + (r >> 2)][r & 3] - 2 * dot;
-                if (__builtin_amdgcn_ballot_w64(u <= thr) != 0) {
-                    const bool row_ok = ((tv[half * 4 + (r >> 2)] >> (8 * (r & 3))) & 0xffu) != 0;
-                    top2_insert_i(row_ok, nq + u, jbase + tr, d1, i1, d2, i2);
-                    thr = d2 - nq;
+                    for (int k = 0; k < kN; ++k) comp[k] = *reinterpret_cast<const f4v*>(&stp[buf][kMatchT * k + tr0]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        float sp[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                        for (int k = 0; k < kN; ++k) sp[k] = comp[k][e];
+                        const bool ok = kCross ? Guide::tail(sp, own, ga.thr2) : Guide::tail(own, sp, ga.thr2);
+                        adm |= ok ? (1u << (16 * (g >> 2) + 4 * (g & 3) + e)) : 0u;
+                    }
+                }
+            };
+            if (swapped) form_bits(std::true_type{});
+            else form_bits(std::false_type{});
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                const unsigned bits = (adm >> (16 * half)) & 0xffffu;
+                if (__builtin_amdgcn_ballot_w64(bits != 0u) == 0) continue;   // no lane of the wave admits a row of this half
+                const unsigned char* trow = half ? t1row : t0row;
+                i4v a[4], tn[4];
+                unsigned tv[4];
+#pragma unroll
+                for (int s = 0; s < 4; ++s) a[s] = *reinterpret_cast<const i4v*>(trow + 32 * s);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int tr0 = half * 32 + 8 * g + 4 * h;
+                    tn[g] = *reinterpret_cast<const i4v*>(&stn[buf][tr0]);
+                    tv[g] = *reinterpret_cast<const unsigned*>(&stv[buf][tr0]);
+                }
+                i16v acc;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = 0;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], b[s], acc, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {   // the element map of the unguided path below
+                    const int tr = half * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int u = tn[r >> 2][r & 3] - 2 * acc[r];
+                    const bool ok = ((bits >> r) & 1u) != 0;
+                    if (__builtin_amdgcn_ballot_w64(ok & (u <= thr)) != 0) {
+                        const bool row_ok = ((tv[r >> 2] >> (8 * (r & 3))) & 0xffu) != 0;
+                        top2_insert_i(row_ok & ok, nq + u, jbase + tr, d1, i1, d2, i2);
+                        thr = d2 - nq;
+                    }
+                }
+            }
+        } else {
+            i4v a0[4], a1[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                a0[s] = *reinterpret_cast<const i4v*>(t0row + 32 * s);
+                a1[s] = *reinterpret_cast<const i4v*>(t1row + 32 * s);
+            }
+            // the norms and valid flags of this lane's 32 train rows (4 consecutive rows per read), on their way during the products
+            i4v tn[8];
+            unsigned tv[8];
+#pragma unroll
+            for (int g = 0; g < 8; ++g) {
+                const int tr0 = (g >> 2) * 32 + 8 * (g & 3) + 4 * h;
+                tn[g] = *reinterpret_cast<const i4v*>(&stn[buf][tr0]);
+                tv[g] = *reinterpret_cast<const unsigned*>(&stv[buf][tr0]);
+            }
+            i16v acc0, acc1;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { acc0[r] = 0; acc1[r] = 0; }
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {   // k = 32 s .. 32 s + 31 into the same accumulators
+                acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0[s], b[s], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1[s], b[s], acc1, 0, 0, 0);
+            }
+            // result element r of lane (c, h): train row (r & 3) + 8 (r >> 2) + 4 h of the half, query row c of the wave's 32.
+            // Once a few hundred rows have been seen nearly every candidate is farther than the lane's second best: the wave
+            // forms n'(b) - 2 dot' and leaves the rest (masks, the order) to the few elements where some lane is not beyond it.
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int tr = half * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int dot = half ? acc1[r] : acc0[r];
+                    const int u = tn[half * 4 + (r >> 2)][r & 3] - 2 * dot;
+                    if (__builtin_amdgcn_ballot_w64(u <= thr) != 0) {
+                        const bool row_ok = ((tv[half * 4 + (r >> 2)] >> (8 * (r & 3))) & 0xffu) != 0;
+                        top2_insert_i(row_ok, nq + u, jbase + tr, d1, i1, d2, i2);
+                        thr = d2 - nq;
+                    }
                 }
             }
         }
@@ -255,7 +362,18 @@ void launch_match_quantize_norms(hipStream_t s, const float* d_desc, const sift_
 void launch_match_tiles_u8(hipStream_t s, const uint8_t* d_desc8, const int32_t* d_norm, const uint8_t* d_valid, const MatchTile* d_tiles,
                            int n_tiles, MatchTop2* d_part) {
     if (n_tiles <= 0) return;
-    hipLaunchKernelGGL(match_tile_u8_kernel, dim3((unsigned)n_tiles), dim3(256), 0, s, d_desc8, d_norm, d_valid, d_tiles, d_part);
+    hipLaunchKernelGGL(match_tile_u8_kernel<NoGuide>, dim3((unsigned)n_tiles), dim3(256), 0, s, d_desc8, d_norm, d_valid, d_tiles, d_part,
+                       MatchGuideArgs{});
+}
+void launch_match_tiles_u8_guided(hipStream_t s, const uint8_t* d_desc8, const int32_t* d_norm, const uint8_t* d_valid, const MatchTile* d_tiles,
+                                  int n_tiles, MatchTop2* d_part, int model, const MatchGuideArgs& ga) {
+    if (n_tiles <= 0) return;
+    if (model == SIFT_HIP_GUIDE_FUNDAMENTAL)
+        hipLaunchKernelGGL(match_tile_u8_kernel<FundamentalGuide>, dim3((unsigned)n_tiles), dim3(256), 0, s, d_desc8, d_norm, d_valid, d_tiles,
+                           d_part, ga);
+    else
+        hipLaunchKernelGGL(match_tile_u8_kernel<HomographyGuide>, dim3((unsigned)n_tiles), dim3(256), 0, s, d_desc8, d_norm, d_valid, d_tiles,
+                           d_part, ga);
 }
 
 }  // namespace sift_hip

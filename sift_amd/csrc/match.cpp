@@ -1,5 +1,5 @@
-// Host side of descriptor matching (include/sift_hip.h: sift_hip_knn2, sift_hip_match, sift_hip_result_match, and their guided
-// counterparts sift_hip_knn2_guided, sift_hip_match_guided, sift_hip_result_match_guided): staging of
+// Host side of descriptor matching (include/sift_hip.h: sift_hip_knn2, sift_hip_match, sift_hip_result_match, their guided
+// counterparts sift_hip_knn2_guided, sift_hip_match_guided, sift_hip_result_match_guided, and the _u8 forms of all six): staging of
 // caller memory, the tile table that makes many pairs one launch, and the scratch memory, which the first match call of a
 // context allocates and the context keeps - outside the batch arena, so a context that never matches allocates nothing here.
 #include <algorithm>
@@ -71,6 +71,7 @@ struct Job {
     const float* ctx_xy = nullptr;   // the result call's after sift_hip_result_localize with use = 1: the points, already built
     const uint8_t* desc8 = nullptr;   // sift_hip_knn2_u8 / sift_hip_match_u8: byte rows in place of `desc`
     bool is_u8 = false;
+    bool quantize_rows = false;   // sift_hip_result_match_guided_u8: the context's float rows become bytes, whatever params->quantized says
 };
 
 int fail(const Job& j, const char* msg) {
@@ -127,8 +128,9 @@ int run(void* arg) {
     float ratio2 = 0.0f;
     if (j.params) {
         if (j.params->quantized > 1) return fail(j, "sift_hip match: quantized must be 0 (float rows) or 1 (8-bit rows, integer distances)");
-        quantized = j.params->quantized == 1;
-        if (quantized && j.guided) return fail(j, "sift_hip match: quantized = 1 is not available in guided matching (float rows only)");
+        quantized = j.params->quantized == 1 || j.quantize_rows;
+        if (quantized && j.guided && !j.is_u8 && !j.quantize_rows)
+            return fail(j, "sift_hip match: quantized = 1 is not available in guided matching over float rows (the _guided_u8 calls take bytes)");
         const float r = j.params->ratio;
         if (!(r >= 0.0f && r <= 1.0f)) return fail(j, "sift_hip match: ratio must be 0 (no ratio test) or in (0, 1]");
         use_ratio = r != 0.0f;
@@ -284,8 +286,12 @@ int run(void* arg) {
             launch_match_norms_u8(v.stream, d_desc8, d_kp, rows, st.d_norm.as<int32_t>(), st.d_valid.as<uint8_t>());
         else
             launch_match_quantize_norms(v.stream, d_desc, d_kp, rows, st.d_desc8.as<uint8_t>(), st.d_norm.as<int32_t>(), st.d_valid.as<uint8_t>());
-        launch_match_tiles_u8(v.stream, d_desc8, st.d_norm.as<int32_t>(), st.d_valid.as<uint8_t>(), st.d_tiles.as<MatchTile>(), (int)tiles.size(),
-                              st.d_part.as<MatchTop2>());
+        if (j.guided)
+            launch_match_tiles_u8_guided(v.stream, d_desc8, st.d_norm.as<int32_t>(), st.d_valid.as<uint8_t>(), st.d_tiles.as<MatchTile>(),
+                                         (int)tiles.size(), st.d_part.as<MatchTop2>(), (int)j.guide->model, ga);
+        else
+            launch_match_tiles_u8(v.stream, d_desc8, st.d_norm.as<int32_t>(), st.d_valid.as<uint8_t>(), st.d_tiles.as<MatchTile>(),
+                                  (int)tiles.size(), st.d_part.as<MatchTop2>());
     } else {
         launch_match_norms(v.stream, d_desc, d_kp, rows, st.d_norm.as<float>(), st.d_valid.as<uint8_t>());
         if (j.guided)
@@ -387,20 +393,23 @@ int match_result_on_device(sift_hip_ctx* c, const char* who, int n_pairs, const 
 }
 }  // namespace sift_hip
 
-// sift_hip_result_match_guided: the images' rows of the device-resident results, their points built from the keypoints
-static int result_match_guided(sift_hip_ctx* c, int n_pairs, const int32_t* pair_q, const int32_t* pair_t, const sift_hip_match_params* params,
+// sift_hip_result_match_guided and its _u8 form (u8: the rows are quantised on the way): the images' rows of the device-resident
+// results, their points built from the keypoints
+static int result_match_guided(sift_hip_ctx* c, bool u8, int n_pairs, const int32_t* pair_q, const int32_t* pair_t, const sift_hip_match_params* params,
                                const sift_hip_guide_params* guide, const float* models, sift_hip_match_rec* recs, int32_t* counts, int64_t* total,
                                char* err, int errlen) {
     using namespace sift_hip;
     const MatchCtxView v = match_ctx_view(c);
     if (!v.have_result) {
-        match_set_err(err, errlen, "sift_hip_result_match_guided: the context holds no results");
+        match_set_err(err, errlen, u8 ? "sift_hip_result_match_guided_u8: the context holds no results"
+                                      : "sift_hip_result_match_guided: the context holds no results");
         return SIFT_HIP_EINVAL;
     }
     std::vector<int64_t> offsets((size_t)v.n_images + 1, 0);
     for (int i = 0; i < v.n_images; ++i) offsets[(size_t)i + 1] = offsets[(size_t)i] + v.counts[i];
     Job j{c, v.d_desc, v.d_kp, true, v.n_images, offsets.data(), n_pairs, pair_q, pair_t, params, nullptr, nullptr, recs, counts, total, err, errlen};
     j.guided = true;
+    j.quantize_rows = u8;
     j.guide = guide;
     j.models = models;
     j.coord_scale = ransac_ctx_subpixel(c) ? 0.5f : 1.0f;
@@ -466,7 +475,7 @@ int sift_hip_result_match_guided(sift_hip_ctx* c, int n_pairs, const int32_t* pa
                                  int64_t* total, char* err, int errlen) {
     if (!c) { match_set_err(err, errlen, "sift_hip_result_match_guided: no context (matching runs on the GPU only)"); return SIFT_HIP_EINVAL; }
     if (!params) { match_set_err(err, errlen, "sift_hip_result_match_guided: no parameters"); return SIFT_HIP_EINVAL; }
-    return result_match_guided(c, n_pairs, pair_q, pair_t, params, guide, models, recs, counts, total, err, errlen);
+    return result_match_guided(c, false, n_pairs, pair_q, pair_t, params, guide, models, recs, counts, total, err, errlen);
 }
 
 int sift_hip_quantize(sift_hip_ctx* c, const float* desc, int64_t rows, uint8_t* out, char* err, int errlen) {
@@ -506,6 +515,44 @@ int sift_hip_match_u8(sift_hip_ctx* c, const uint8_t* desc, const sift_hip_keypo
     j.desc8 = desc;
     j.is_u8 = true;
     return match_guarded(err, errlen, run, &j);
+}
+
+int sift_hip_knn2_guided_u8(sift_hip_ctx* c, const uint8_t* desc, const sift_hip_keypoint* kp, const float* xy, int n_sets, const int64_t* offsets,
+                            int n_pairs, const int32_t* pair_q, const int32_t* pair_t, const sift_hip_guide_params* guide, const float* models,
+                            int32_t* idx, float* dist2, char* err, int errlen) {
+    if (!c) { match_set_err(err, errlen, "sift_hip_knn2_guided_u8: no context (matching runs on the GPU only)"); return SIFT_HIP_EINVAL; }
+    Job j{c, nullptr, kp, false, n_sets, offsets, n_pairs, pair_q, pair_t, nullptr, idx, dist2, nullptr, nullptr, nullptr, err, errlen};
+    j.desc8 = desc;
+    j.is_u8 = true;
+    j.guided = true;
+    j.xy = xy;
+    j.guide = guide;
+    j.models = models;
+    return match_guarded(err, errlen, run, &j);
+}
+
+int sift_hip_match_guided_u8(sift_hip_ctx* c, const uint8_t* desc, const sift_hip_keypoint* kp, const float* xy, int n_sets,
+                             const int64_t* offsets, int n_pairs, const int32_t* pair_q, const int32_t* pair_t,
+                             const sift_hip_match_params* params, const sift_hip_guide_params* guide, const float* models,
+                             sift_hip_match_rec* recs, int32_t* counts, int64_t* total, char* err, int errlen) {
+    if (!c) { match_set_err(err, errlen, "sift_hip_match_guided_u8: no context (matching runs on the GPU only)"); return SIFT_HIP_EINVAL; }
+    if (!params) { match_set_err(err, errlen, "sift_hip_match_guided_u8: no parameters"); return SIFT_HIP_EINVAL; }
+    Job j{c, nullptr, kp, false, n_sets, offsets, n_pairs, pair_q, pair_t, params, nullptr, nullptr, recs, counts, total, err, errlen};
+    j.desc8 = desc;
+    j.is_u8 = true;
+    j.guided = true;
+    j.xy = xy;
+    j.guide = guide;
+    j.models = models;
+    return match_guarded(err, errlen, run, &j);
+}
+
+int sift_hip_result_match_guided_u8(sift_hip_ctx* c, int n_pairs, const int32_t* pair_q, const int32_t* pair_t,
+                                    const sift_hip_match_params* params, const sift_hip_guide_params* guide, const float* models,
+                                    sift_hip_match_rec* recs, int32_t* counts, int64_t* total, char* err, int errlen) {
+    if (!c) { match_set_err(err, errlen, "sift_hip_result_match_guided_u8: no context (matching runs on the GPU only)"); return SIFT_HIP_EINVAL; }
+    if (!params) { match_set_err(err, errlen, "sift_hip_result_match_guided_u8: no parameters"); return SIFT_HIP_EINVAL; }
+    return result_match_guided(c, true, n_pairs, pair_q, pair_t, params, guide, models, recs, counts, total, err, errlen);
 }
 
 }  // extern "C"

@@ -69,6 +69,9 @@ void launch_match_quantize_norms(hipStream_t s, const float* d_desc, const sift_
 // the tile kernel on the i8 matrix instruction: the tables and the partials of launch_match_tiles, distances as (float)d2
 void launch_match_tiles_u8(hipStream_t s, const uint8_t* d_desc8, const int32_t* d_norm, const uint8_t* d_valid, const MatchTile* d_tiles,
                            int n_tiles, MatchTop2* d_part);
+// the same under the pairs' models ("guided matching on 8-bit descriptors"); model and ga as for launch_match_tiles_guided
+void launch_match_tiles_u8_guided(hipStream_t s, const uint8_t* d_desc8, const int32_t* d_norm, const uint8_t* d_valid, const MatchTile* d_tiles,
+                                  int n_tiles, MatchTop2* d_part, int model, const MatchGuideArgs& ga);
 
 // scratch of the matcher and of the geometric verification (ransac.cpp): device memory that only grows, kept with the context
 struct ScratchBuf {

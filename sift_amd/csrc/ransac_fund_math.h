@@ -278,4 +278,28 @@ SIFT_HD bool ransac_fund_inlier(const float (&f)[9], float qx, float qy, float t
     return (e <= thr2 * g) & (g > 0.0f) & (e < __builtin_inff());
 }
 
+// ransac_fund_inlier split by point, as ransac_inlier_query / _train / _tail split ransac_inlier: the query part is a, b, c (the
+// line F q), the train part is the point and u = a2^2 + b2^2 (the first two entries of F^T t, squared and summed as the innermost
+// fmaf of g), the tail is what needs both.  The same operations in the same order: the same bit.
+SIFT_HD void ransac_fund_inlier_query(const float (&f)[9], float qx, float qy, float, float (&p)[4]) {
+    p[0] = __builtin_fmaf(f[0], qx, __builtin_fmaf(f[1], qy, f[2]));
+    p[1] = __builtin_fmaf(f[3], qx, __builtin_fmaf(f[4], qy, f[5]));
+    p[2] = __builtin_fmaf(f[6], qx, __builtin_fmaf(f[7], qy, f[8]));
+    p[3] = 0.0f;
+}
+SIFT_HD void ransac_fund_inlier_train(const float (&f)[9], float tx, float ty, float (&p)[4]) {
+    const float a2 = __builtin_fmaf(f[0], tx, __builtin_fmaf(f[3], ty, f[6]));
+    const float b2 = __builtin_fmaf(f[1], tx, __builtin_fmaf(f[4], ty, f[7]));
+    p[0] = tx;
+    p[1] = ty;
+    p[2] = __builtin_fmaf(a2, a2, b2 * b2);
+    p[3] = 0.0f;
+}
+SIFT_HD bool ransac_fund_inlier_tail(const float (&q)[4], const float (&t)[4], float thr2) {
+    const float r = __builtin_fmaf(t[0], q[0], __builtin_fmaf(t[1], q[1], q[2]));
+    const float g = __builtin_fmaf(q[0], q[0], __builtin_fmaf(q[1], q[1], t[2]));
+    const float e = r * r;
+    return (e <= thr2 * g) & (g > 0.0f) & (e < __builtin_inff());
+}
+
 }  // namespace sift_hip

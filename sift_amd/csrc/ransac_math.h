@@ -171,4 +171,28 @@ SIFT_HD bool ransac_inlier(const float (&h)[9], float qx, float qy, float tx, fl
     return (W > 0.0f) & (e2 <= bound) & (e2 < __builtin_inff());
 }
 
+// ransac_inlier split by point, for a caller that tests one query point against many train points or the reverse (the guided
+// 8-bit tile kernel, kernels_match_u8.hip): the same operations in the same order, so the same bit.  The query part is X, Y, W
+// and the bound; W > 0 travels inside the bound - a NaN bound fails the tail's first compare as !(W > 0) fails the predicate.
+// The train part is the point itself.  Parts are four floats; unused ones are +0.0f.
+SIFT_HD void ransac_inlier_query(const float (&h)[9], float qx, float qy, float thr2, float (&p)[4]) {
+    p[0] = __builtin_fmaf(h[0], qx, __builtin_fmaf(h[1], qy, h[2]));
+    p[1] = __builtin_fmaf(h[3], qx, __builtin_fmaf(h[4], qy, h[5]));
+    p[2] = __builtin_fmaf(h[6], qx, __builtin_fmaf(h[7], qy, h[8]));
+    const float bound = thr2 * (p[2] * p[2]);
+    p[3] = p[2] > 0.0f ? bound : __builtin_nanf("");
+}
+SIFT_HD void ransac_inlier_train(const float (&)[9], float tx, float ty, float (&p)[4]) {
+    p[0] = tx;
+    p[1] = ty;
+    p[2] = 0.0f;
+    p[3] = 0.0f;
+}
+SIFT_HD bool ransac_inlier_tail(const float (&q)[4], const float (&t)[4], float) {
+    const float ex = __builtin_fmaf(-t[0], q[2], q[0]);
+    const float ey = __builtin_fmaf(-t[1], q[2], q[1]);
+    const float e2 = __builtin_fmaf(ex, ex, ey * ey);
+    return (e2 <= q[3]) & (e2 < __builtin_inff());
+}
+
 }  // namespace sift_hip

@@ -580,19 +580,23 @@ class Context:
         """sift_hip_knn2_guided: knn2_sets among the train rows that are admissible under the pair's model -> (idx, dist2).  `xy`:
         two floats per row of `desc`; `models`: one per pair, a HOMOGRAPHY_DTYPE / FUNDAMENTAL_DTYPE array or [n_pairs, 9] floats;
         xy and models may be numpy arrays, tensors or addresses (host or device memory)."""
+        return self._knn2_guided_sets(self._L.sift_hip_knn2_guided, np.float32, desc, xy, offsets, pairs, models, model, threshold, kp, idx_out,
+                                      dist_out)
+
+    def _knn2_guided_sets(self, call, dtype, desc, xy, offsets, pairs, models, model, threshold, kp, idx_out, dist_out):
         offsets = np.ascontiguousarray(offsets, np.int64)
         pq, pt = self._pairs(pairs)
         rows = int(sum(offsets[q + 1] - offsets[q] for q in pq if 0 <= q < offsets.size - 1))
         idx = np.full((rows, 2), -1, np.int32) if idx_out is None else idx_out
         dist = np.full((rows, 2), np.inf, np.float32) if dist_out is None else dist_out
         if isinstance(desc, np.ndarray):
-            desc = np.ascontiguousarray(desc, np.float32)
+            desc = self._rows(desc, dtype)
         if isinstance(xy, np.ndarray):
             xy = np.ascontiguousarray(xy, np.float32)
         prm = self._guide(model, threshold)
         models = self._models9(models, pq.size)
         err = C.create_string_buffer(512)
-        rc = self._L.sift_hip_knn2_guided(self._h, self._addr(desc), self._addr(kp), self._addr(xy), offsets.size - 1, offsets, pq.size, pq, pt,
+        rc = call(self._h, self._addr(desc), self._addr(kp), self._addr(xy), offsets.size - 1, offsets, pq.size, pq, pt,
                                           C.byref(prm), self._addr(models), self._addr(idx), self._addr(dist), err, 512)
         if rc:
             _raise(rc, err)
@@ -610,7 +614,11 @@ class Context:
     def match_guided_sets(self, desc, xy, offsets, pairs, models, model="homography", threshold=3.0, ratio=0.8, cross_check=False, kp=None,
                           recs_out=None, quantized=False):
         """sift_hip_match_guided: match_sets under the pairs' models -> (records, counts).  Arguments as for knn2_guided_sets and
-        match_sets.  Guided matching takes float rows only: `quantized=True` is a ValueError (the call says so)."""
+        match_sets.  This call takes float rows only: `quantized=True` is a ValueError (the call says so; match_guided_sets_u8)."""
+        return self._match_guided_sets(self._L.sift_hip_match_guided, np.float32, desc, xy, offsets, pairs, models, model, threshold, ratio,
+                                       cross_check, kp, recs_out, quantized)
+
+    def _match_guided_sets(self, call, dtype, desc, xy, offsets, pairs, models, model, threshold, ratio, cross_check, kp, recs_out, quantized):
         offsets = np.ascontiguousarray(offsets, np.int64)
         pq, pt = self._pairs(pairs)
         rows = int(sum(offsets[q + 1] - offsets[q] for q in pq if 0 <= q < offsets.size - 1))
@@ -618,14 +626,14 @@ class Context:
         counts = np.zeros(pq.size, np.int32)
         total = C.c_int64()
         if isinstance(desc, np.ndarray):
-            desc = np.ascontiguousarray(desc, np.float32)
+            desc = self._rows(desc, dtype)
         if isinstance(xy, np.ndarray):
             xy = np.ascontiguousarray(xy, np.float32)
         mprm = _lib.MatchParams(float(ratio), 1 if cross_check else 0, self._quantized(quantized))
         gprm = self._guide(model, threshold)
         models = self._models9(models, pq.size)
         err = C.create_string_buffer(512)
-        rc = self._L.sift_hip_match_guided(self._h, self._addr(desc), self._addr(kp), self._addr(xy), offsets.size - 1, offsets, pq.size, pq, pt,
+        rc = call(self._h, self._addr(desc), self._addr(kp), self._addr(xy), offsets.size - 1, offsets, pq.size, pq, pt,
                                            C.byref(mprm), C.byref(gprm), self._addr(models), self._addr(recs), counts, C.byref(total), err, 512)
         if rc:
             _raise(rc, err)
@@ -646,6 +654,10 @@ class Context:
         """sift_hip_result_match_guided: match_images under the pairs' models, e.g. those verify_images returned, on the
         device-resident results (the keypoints' image coordinates are built on the GPU) -> (records, counts).  `quantized=True`
         is a ValueError, as for match_guided_sets.  `localized`: localize(use=True) first - the points are the sub-pixel ones."""
+        return self._match_images_guided(self._L.sift_hip_result_match_guided, pairs, models, model, threshold, ratio, cross_check, quantized,
+                                         localized)
+
+    def _match_images_guided(self, call, pairs, models, model, threshold, ratio, cross_check, quantized, localized):
         if localized:
             self.localize(use=True)
         pq, pt = self._pairs(pairs)
@@ -658,11 +670,48 @@ class Context:
         gprm = self._guide(model, threshold)
         models = self._models9(models, pq.size)
         err = C.create_string_buffer(512)
-        rc = self._L.sift_hip_result_match_guided(self._h, pq.size, pq, pt, C.byref(mprm), C.byref(gprm), self._addr(models),
-                                                  C.c_void_p(recs.ctypes.data), counts, C.byref(total), err, 512)
+        rc = call(self._h, pq.size, pq, pt, C.byref(mprm), C.byref(gprm), self._addr(models), C.c_void_p(recs.ctypes.data), counts,
+                  C.byref(total), err, 512)
         if rc:
             _raise(rc, err)
         return recs[:total.value], counts
+
+    # ---- guided matching on 8-bit descriptors (include/sift_hip.h) ------------------------------------------
+    def knn2_guided_sets_u8(self, desc, xy, offsets, pairs, models, model="homography", threshold=3.0, kp=None, idx_out=None, dist_out=None):
+        """sift_hip_knn2_guided_u8: knn2_guided_sets over uint8 rows; the distances are the exact integers of knn2_sets_u8."""
+        return self._knn2_guided_sets(self._L.sift_hip_knn2_guided_u8, np.uint8, desc, xy, offsets, pairs, models, model, threshold, kp, idx_out,
+                                      dist_out)
+
+    def knn2_guided_u8(self, q, t, q_xy, t_xy, model_matrix, model="homography", threshold=3.0, q_kp=None, t_kp=None):
+        """knn2_guided over uint8 rows `q` [nq, 128] and `t` [nt, 128] (numpy, host memory)."""
+        q = self._rows(np.asarray(q), np.uint8).reshape(-1, 128)
+        t = self._rows(np.asarray(t), np.uint8).reshape(-1, 128)
+        desc, offsets, kp = self._two_sets(q, t, q_kp, t_kp)
+        xy = np.concatenate([np.asarray(q_xy, np.float32).reshape(-1, 2), np.asarray(t_xy, np.float32).reshape(-1, 2)])
+        return self.knn2_guided_sets_u8(desc, xy, offsets, [(0, 1)], np.asarray(model_matrix, np.float32).reshape(1, 9), model, threshold, kp)
+
+    def match_guided_sets_u8(self, desc, xy, offsets, pairs, models, model="homography", threshold=3.0, ratio=0.8, cross_check=False, kp=None,
+                             recs_out=None, quantized=True):
+        """sift_hip_match_guided_u8: match_guided_sets over uint8 rows -> (records, counts).  `quantized` is the byte of the
+        parameters: False and True both mean bytes here, a number above 1 is a ValueError (the call says so)."""
+        return self._match_guided_sets(self._L.sift_hip_match_guided_u8, np.uint8, desc, xy, offsets, pairs, models, model, threshold, ratio,
+                                       cross_check, kp, recs_out, quantized)
+
+    def match_guided_u8(self, q, t, q_xy, t_xy, model_matrix, model="homography", threshold=3.0, ratio=0.8, cross_check=False, q_kp=None,
+                        t_kp=None):
+        """match_guided over uint8 rows (numpy, host memory): records in query order."""
+        q = self._rows(np.asarray(q), np.uint8).reshape(-1, 128)
+        t = self._rows(np.asarray(t), np.uint8).reshape(-1, 128)
+        desc, offsets, kp = self._two_sets(q, t, q_kp, t_kp)
+        xy = np.concatenate([np.asarray(q_xy, np.float32).reshape(-1, 2), np.asarray(t_xy, np.float32).reshape(-1, 2)])
+        return self.match_guided_sets_u8(desc, xy, offsets, [(0, 1)], np.asarray(model_matrix, np.float32).reshape(1, 9), model, threshold,
+                                         ratio, cross_check, kp)[0]
+
+    def match_images_guided_u8(self, pairs, models, model="homography", threshold=3.0, ratio=0.8, cross_check=False, localized=False):
+        """sift_hip_result_match_guided_u8: match_images_guided over the results' descriptors quantised to 8 bits on the device
+        (match_guided_sets_u8 of results_u8() and the same coordinates) -> (records, counts)."""
+        return self._match_images_guided(self._L.sift_hip_result_match_guided_u8, pairs, models, model, threshold, ratio, cross_check, True,
+                                         localized)
 
     # ---- geometric verification (include/sift_hip.h, "geometric verification") ----------------------------
     def ransac_homography(self, pts, offsets=None, iterations=2048, threshold=3.0, seed=0, want_scores=False, models_out=None,
@@ -1043,10 +1092,12 @@ class Sift:
         models, refined, inlier = self.ctx.refine_fundamental(pts, None, np.asarray(model).reshape(1), threshold, rounds)
         return models[0], int(refined[0]), inlier
 
-    def match_guided(self, points_a, points_b, model, threshold: float = 3.0, ratio: float = 0.8, cross_check: bool = False, localized=None):
+    def match_guided(self, points_a, points_b, model, threshold: float = 3.0, ratio: float = 0.8, cross_check: bool = False, localized=None,
+                     quantized: bool = False):
         """match() again under the model verify() returned (an extension): a point of b competes for a point of a only when it
         lies within `threshold` pixels of the model - of the transferred point (a homography record) or of the epipolar line (a
-        fundamental record).  Coordinates, and `localized`, as for verify().  A model that is none (all zeros) gives no records."""
+        fundamental record).  Coordinates, and `localized`, as for verify().  A model that is none (all zeros) gives no records.
+        `quantized`: the descriptors are quantised to 8 bits on the GPU and matched by the integer distance, as for match()."""
         names = getattr(getattr(model, "dtype", None), "names", None) or ()
         if "h" not in names and "f" not in names:
             raise ValueError("match_guided: model must be a record as verify() returns it")
@@ -1062,5 +1113,7 @@ class Sift:
             return d, kp, self._coords(points, range(len(points)), localized, side)
         qa, ka, xa = rows(points_a, 0)
         qb, kb, xb = rows(points_b, 1)
-        return self.ctx.match_guided(qa, qb, xa, xb, np.asarray(model["h" if kind == "homography" else "f"], np.float32), kind, threshold,
-                                     ratio, cross_check, ka, kb)
+        m9 = np.asarray(model["h" if kind == "homography" else "f"], np.float32)
+        if quantized:
+            return self.ctx.match_guided_u8(self.ctx.quantize(qa), self.ctx.quantize(qb), xa, xb, m9, kind, threshold, ratio, cross_check, ka, kb)
+        return self.ctx.match_guided(qa, qb, xa, xb, m9, kind, threshold, ratio, cross_check, ka, kb)

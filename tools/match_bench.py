@@ -25,6 +25,11 @@ of case (a) on device-resident rows (sift_hip_knn2 on the float results against 
 without and with the cross-check (sift_hip_result_match with quantized = 0 against quantized = 1, which includes the quantiser's
 pass).  256 sampled query rows of (a) are compared bit for bit with the integer host checker.  Median, min and max of --reps, the
 ratio of the medians, and whether the two min - max intervals overlap (then there is no winner); lines are appended to --out.
+
+--guided-u8-arm: the cases and the three guides of --guided-arm, sift_hip_result_match_guided (f32) alternating with
+sift_hip_result_match_guided_u8 in the same run, and sift_hip_result_match with quantized = 1 as the unguided 8-bit arm.  On (a),
+256 sampled query rows of sift_hip_knn2_guided_u8 under the fixed homography are compared bit for bit with the host checker.
+--unguided-only --quantized: the unguided 8-bit calls alone (for an A/B of two builds).
 """
 import argparse
 import json
@@ -53,6 +58,8 @@ def main():
     ap.add_argument("--guided-arm", action="store_true")
     ap.add_argument("--unguided-only", action="store_true")
     ap.add_argument("--u8-arm", action="store_true")
+    ap.add_argument("--guided-u8-arm", action="store_true")
+    ap.add_argument("--quantized", action="store_true")
     args = ap.parse_args()
 
     import torch
@@ -115,9 +122,29 @@ def main():
         f_all = np.array([0, 0, 1, 0, 0, 0, 0, 0, 0], np.float32)            # a = 1, b = 0: g > 0 at every row
         f_rows = np.array([0, 0, 0, 0, 0, -1, 0, 1, 0], np.float32)          # epipolar lines ty = qy
         n = cnt.size
+        both = args.guided_u8_arm
+        f32 = " f32" if both else ""
+        if both:   # spot check: 256 query rows of frame 1 under the fixed homography at 3 px against the host checker
+            import ctypes as C
+            import match_u8_ref as U
+            kp, d8 = ctx.results_u8()
+            off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+            xy = np.stack([(kp["x"].astype(np.uint32) << kp["octave"]).astype(np.float32),
+                           (kp["y"].astype(np.uint32) << kp["octave"]).astype(np.float32)], axis=1)
+            rows = np.sort(np.random.default_rng(0).choice(int(cnt[0]), size=min(256, int(cnt[0])), replace=False))
+            got = ctx.knn2_guided_sets_u8(d8, xy, off, [(0, 1)], identity.reshape(1, 9), "homography", 3.0, kp)
+            v = kp["has_descriptor"]
+            host = [np.ascontiguousarray(a) for a in (d8[:off[1]][rows], v[:off[1]][rows], xy[:off[1]][rows], d8[off[1]:off[2]], v[off[1]:off[2]],
+                                                      xy[off[1]:off[2]], identity)]
+            want = np.zeros((rows.size, 2), np.int32), np.zeros((rows.size, 2), np.float32)
+            q8, qv, qxy, t8, tv, txy, m9 = [C.c_void_p(a.ctypes.data) for a in host]
+            U.hostmath().hostmath_match_knn2_guided_u8(q8, qv, qxy, C.c_longlong(rows.size), t8, tv, txy, C.c_longlong(int(cnt[1])), 0, m9,
+                                                       C.c_float(3.0), 0, C.c_void_p(want[0].ctypes.data), C.c_void_p(want[1].ctypes.data))
+            emit({"case": "guided u8 arm, spot check of 256 rows of (a), fixed homography 3 px", "rows_with_a_match": int((want[0][:, 0] >= 0).sum()),
+                  "bitwise": bool(M.same_bits(got[0][rows], want[0]) and M.same_bits(got[1][rows], want[1]))})
         for name, pairs in (("a: frames 1 and 2", [(0, 1)]), (f"b: the {n - 1} consecutive pairs", [(i, i + 1) for i in range(n - 1)])):
             for cross in (False, True):
-                arms = {"unguided": lambda: ctx.match_images(pairs, 0.8, cross)}
+                arms = {"unguided u8" if both or args.quantized else "unguided": lambda: ctx.match_images(pairs, 0.8, cross, both or args.quantized)}
                 if args.unguided_only:
                     emit({"case": name, "cross_check": cross, "library": os.path.basename(_lib.LIB_PATH), **timed(arms)})
                     continue
@@ -125,12 +152,13 @@ def main():
                 for kind, every, fixed in (("homography", identity, identity), ("fundamental", f_all, f_rows)):
                     models = ctx.verify_images(pairs, 0.8, cross, 512, 3.0, 0, model=kind)[2]
                     tile = lambda m: np.tile(m, (len(pairs), 1))   # noqa: E731
-                    arms[kind + " verified 3 px"] = lambda m=models, k=kind: ctx.match_images_guided(pairs, m, k, 3.0, 0.8, cross)
-                    arms[kind + " admit-all"] = lambda m=tile(every), k=kind: ctx.match_images_guided(pairs, m, k, 1e30, 0.8, cross)
-                    arms[kind + " fixed model 3 px"] = lambda m=tile(fixed), k=kind: ctx.match_images_guided(pairs, m, k, 3.0, 0.8, cross)
+                    for guide, m, thr in ((" verified 3 px", models, 3.0), (" admit-all", tile(every), 1e30), (" fixed model 3 px", tile(fixed), 3.0)):
+                        arms[kind + guide + f32] = lambda m=m, k=kind, t=thr: ctx.match_images_guided(pairs, m, k, t, 0.8, cross)
+                        if both:
+                            arms[kind + guide + " u8"] = lambda m=m, k=kind, t=thr: ctx.match_images_guided_u8(pairs, m, k, t, 0.8, cross)
                     found[kind] = int((models["iteration"] >= 0).sum())
                 res = timed(arms)
-                emit({"case": "guided, " + name, "cross_check": cross, "pairs_with_a_verified_model": found,
+                emit({"case": ("guided u8 arm, " if both else "guided, ") + name, "cross_check": cross, "pairs_with_a_verified_model": found,
                       "matches": {k: int(fn()[0].size) for k, fn in arms.items()}, **res})
 
     def u8_arms(ctx, cnt):
@@ -170,7 +198,7 @@ def main():
     n = args.frames
     ctx.calculate_batch(synth_batch(n, 1920, 1080), _lib.Params(3, 4, 1.6, K_SQRT2, 0))
     cnt = ctx.counts()
-    if args.guided_arm or args.unguided_only or args.u8_arm:
+    if args.guided_arm or args.unguided_only or args.u8_arm or args.guided_u8_arm:
         if args.u8_arm:
             u8_arms(ctx, cnt)
         else:
@@ -180,6 +208,8 @@ def main():
             with open(args.out, "a") as f:
                 f.write("# tools/match_bench.py --u8-arm: the float matcher alternating with the 8-bit integer matcher (ms on the host around each call)\n"
                         if args.u8_arm else
+                        "# tools/match_bench.py --guided-u8-arm: sift_hip_result_match_guided alternating with sift_hip_result_match_guided_u8 (ms on the host around each call)\n"
+                        if args.guided_u8_arm else
                         "# tools/match_bench.py --guided-arm: sift_hip_result_match alternating with sift_hip_result_match_guided (ms on the host around each call)\n"
                         if args.guided_arm else "# tools/match_bench.py --unguided-only\n")
                 f.write("\n".join(lines) + "\n")
