@@ -3,7 +3,9 @@
 // or, with model=fundamental, sift::Matcher::verify_fundamental(): a seven-point fundamental matrix, the model for two views of a
 // general scene.  inliers.txt holds the lines of matches.txt that agree with the model.
 //   g++ -std=c++17 -pthread -Iinclude examples/sift_verify.cpp -Lsift_amd/lib -lsift_hip -Wl,-rpath,$PWD/sift_amd/lib -o sift_verify
-//   ./sift_verify a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [refine=0] [model=homography|fundamental] [refit=-1] [localize=0]
+//   ./sift_verify a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [refine=0] [model=homography|fundamental] [refit=-1] [localize=0] [warp out.pgm]
+//   ... warp out.pgm (with model=homography): b registered onto a under the verified model (sift::Matcher::warp), as an 8-bit PGM
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -37,7 +39,7 @@ static void write_matches(const char* path, const std::vector<sift::Match>& matc
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::cerr << "usage: " << argv[0]
-                  << " a.{pgm,ppm,png,jpg} b.{...} [octaves] [dogsPerEpoch] [ratio] [crossCheck] [iterations] [threshold] [seed] [refine] [homography|fundamental] [refit] [localize]\n";
+                  << " a.{pgm,ppm,png,jpg} b.{...} [octaves] [dogsPerEpoch] [ratio] [crossCheck] [iterations] [threshold] [seed] [refine] [homography|fundamental] [refit] [localize] [warp out.pgm]\n";
         return 1;
     }
     const u16_t octaves = argc > 3 ? (u16_t)std::atoi(argv[3]) : 4;
@@ -57,6 +59,12 @@ int main(int argc, char** argv) {
     const int refit = argc > 12 ? std::atoi(argv[12]) : -1;
     // 1: the models are estimated on sub-pixel coordinates (sift::Sift::localize after each calculate, sift::Matcher::localize)
     const bool localize = argc > 13 && std::atoi(argv[13]) != 0;
+    // "warp out.pgm": b resampled on a's pixel grid under the verified homography
+    const std::string warp_file = argc > 15 && std::string(argv[14]) == "warp" ? argv[15] : "";
+    if (!warp_file.empty() && model_name != "homography") {
+        std::cerr << "warp is for model=homography\n";
+        return 1;
+    }
     if (refit >= 0 && model_name != "fundamental") {
         std::cerr << "refit is for model=fundamental\n";
         return 1;
@@ -101,6 +109,25 @@ int main(int argc, char** argv) {
             std::cout << "no homography\n";
         } else {
             for (int r = 0; r < 3; ++r) std::printf("H %.9g %.9g %.9g\n", (double)model.h[3 * r], (double)model.h[3 * r + 1], (double)model.h[3 * r + 2]);
+        }
+        if (!warp_file.empty()) {   // no homography: the all-zero model covers nothing, the picture is black
+            char err[512] = "";
+            int wa = 0, ha = 0, wb = 0, hb = 0;
+            if (sift_hip_image_info(argv[1], &wa, &ha, nullptr, nullptr, err, sizeof(err)) != SIFT_HIP_OK ||
+                sift_hip_image_info(argv[2], &wb, &hb, nullptr, nullptr, err, sizeof(err)) != SIFT_HIP_OK)
+                throw std::runtime_error(err);
+            sift::Image2f train(wb, hb);
+            if (sift_hip_image_read_band0(argv[2], train.data(), (long long)wb * hb, err, sizeof(err)) != SIFT_HIP_OK) throw std::runtime_error(err);
+            sift::Image2f reg = matcher.warp(train, model.h, wa, ha);
+            FILE* out = std::fopen(warp_file.c_str(), "wb");
+            if (!out) throw std::runtime_error("cannot write " + warp_file);
+            std::fprintf(out, "P5\n%d %d\n255\n", wa, ha);
+            for (size_t i = 0; i < (size_t)wa * (size_t)ha; ++i) {   // rounded to nearest even and clamped, like the CLI's PNG
+                const float v = std::nearbyint(reg.data()[i]);
+                std::fputc((int)(v < 0.0f ? 0.0f : v > 255.0f ? 255.0f : v), out);
+            }
+            std::fclose(out);
+            std::cout << argv[2] << " registered -> " << warp_file << "\n";
         }
     } catch (std::exception& ex) {
         std::cerr << ex.what() << std::endl;

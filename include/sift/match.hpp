@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../sift_hip.h"
+#include "image2f.hpp"
 #include "interestpoint.hpp"
 #include "types.hpp"
 
@@ -184,6 +185,30 @@ public:
         _use = true;
     }
     void clear_localize() { _use = false; }
+
+    // The homography warp (include/sift_hip.h, "homography warp"): `train` resampled on an out_w x out_h pixel grid of the query
+    // frame under the nine floats `h` (verify()'s model maps query to train, so it is taken as it comes); output pixel (x, y) is
+    // the query-frame point (x + origin_x, y + origin_y).  Where the train image does not reach: `fill`, and 0 in *covered (may
+    // be null; else one byte per pixel).  A model that is none (all zeros) gives an image of `fill`.  Throws
+    // std::invalid_argument for what sift_hip_warp_homography rejects.
+    Image2f warp(Image2f& train, const f32_t (&h)[9], int out_w, int out_h, int origin_x = 0, int origin_y = 0, f32_t fill = 0.0f,
+                 bool bilinear = true, std::vector<uint8_t>* covered = nullptr) {
+        sift_hip_warp_params prm{};
+        prm.out_w = out_w;
+        prm.out_h = out_h;
+        prm.origin_x = origin_x;
+        prm.origin_y = origin_y;
+        prm.fill = fill;
+        prm.interp = bilinear ? 1 : 0;
+        Image2f out(out_w > 0 ? out_w : 0, out_h > 0 ? out_h : 0);
+        if (covered) covered->assign((size_t)out.width() * (size_t)out.height(), 0);
+        char err[512] = "";
+        const int rc = sift_hip_warp_homography(_ctx, train.data(), 1, (int)train.width(), (int)train.height(), 1, nullptr, h, &prm, out.data(),
+                                                covered ? covered->data() : nullptr, nullptr, err, sizeof(err));
+        if (rc == SIFT_HIP_EINVAL) throw std::invalid_argument(err);
+        if (rc != SIFT_HIP_OK) throw std::runtime_error(err);
+        return out;
+    }
 
 private:
     // the image coordinates of point i of the query (side 0) or train (side 1) list

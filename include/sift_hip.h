@@ -546,6 +546,36 @@ int sift_hip_result_localize(sift_hip_ctx* ctx, int max_moves, int use, sift_hip
 int sift_hip_localize_points(sift_hip_ctx* ctx, const float* dogs, int L, int w, int h, const uint16_t* xs, const uint16_t* ys,
                              const uint16_t* is, int m, int max_moves, sift_hip_localized* out, char* err, int errlen);
 
+/* ---- homography warp (an extension) ------------------------------------------------------------------------
+ * Applies a model to an image: job j resamples image src[j] (w x h floats, row-major) under the nine floats models[9 j ..] into
+ * out[j] (out_h x out_w).  The model maps query to train as above, so warping the TRAIN image into the QUERY frame takes the H
+ * of a verified pair as it comes, with no inverse.  sift_amd/csrc/warp_math.h defines every bit (float operations, explicit
+ * fmaf); the kernel and a plain host loop (hostmath_warp_homography) compile it.  For output pixel (x, y), pixel centres at
+ * integer coordinates: qx = (float)(x + origin_x), qy = (float)(y + origin_y); X, Y, W as the inlier predicate forms them
+ * (ransac_math.h); u = X / W, v = Y / W, the correctly rounded quotients.  The pixel is covered iff W > 0, W < +inf, 0 <= u <=
+ * (float)(w - 1) and 0 <= v <= (float)(h - 1) (a NaN anywhere: not covered).  Not covered: value fill, mask 0.  Covered, mask 1:
+ *   interp 1  x0 = (int)floorf(u), fx = u - (float)x0, x1 = min(x0 + 1, w - 1), rows likewise; top = fmaf(fx, p01 - p00, p00),
+ *             bot = fmaf(fx, p11 - p10, p10), value fmaf(fy, bot - top, top)
+ *   interp 0  the pixel at ((int)floorf(u + 0.5f), (int)floorf(v + 0.5f))
+ * A model of all +0.0f (iteration -1) has W = 0: every pixel is fill.  The result does not depend on `path`, tiles or launch. */
+typedef struct sift_hip_warp_params {
+    int32_t out_w, out_h;        /* > 0 */
+    int32_t origin_x, origin_y;  /* output pixel (x, y) is query-frame point (x + origin_x, y + origin_y): a canvas may exceed the frame */
+    float fill;
+    uint8_t interp;              /* 0 nearest, 1 bilinear; above: EINVAL */
+    uint8_t path;                /* 0: the library chooses per tile; 1: every tile takes the direct path (same bits; measurement and tests) */
+    uint8_t reserved[2];         /* zero */
+} sift_hip_warp_params;          /* 24 bytes */
+/* imgs (n_imgs x h x w), models (n_jobs x 9), out (n_jobs x out_h x out_w) and mask (same shape, bytes; may be NULL) may each
+ * be host or device memory; src (host; NULL: job j warps image j) and tiles (host, may be NULL: [0] tiles that staged their
+ * source footprint in LDS, [1] tiles that read it directly).  Scratch memory is allocated on first use and kept with the
+ * context; the call runs on the context's stream, returns when the results are in place and may not be made while a batch is
+ * in flight.  All jobs share one launch.  SIFT_HIP_EINVAL for a bad size (w, h above 2^22, n_jobs above 65535, a lattice
+ * coordinate of magnitude >= 2^24), interp, path, src index or non-zero reserved bytes. */
+int sift_hip_warp_homography(sift_hip_ctx* ctx, const float* imgs, int n_imgs, int w, int h, int n_jobs, const int32_t* src,
+                             const float* models, const sift_hip_warp_params* params, float* out, uint8_t* mask, int64_t* tiles,
+                             char* err, int errlen);
+
 /* ---- inspection of the last batch (parity tests) ------------------------------------------------ */
 /* kind: 0 gaussian (levels 0..D), 1 dog (0..D-1), 2 magnitude, 3 orientation (initial gradient
  * maps, sift.cpp:130-160, only for levels some keypoint scale selects; 0x0 otherwise). */

@@ -43,6 +43,7 @@ SYMBOLS = [
     "sift_hip_quantize", "sift_hip_result_copy_u8", "sift_hip_knn2_u8", "sift_hip_match_u8",
     "sift_hip_knn2_guided_u8", "sift_hip_match_guided_u8", "sift_hip_result_match_guided_u8",
     "sift_hip_result_localize", "sift_hip_localize_points",
+    "sift_hip_warp_homography",
 ]
 
 
@@ -63,6 +64,14 @@ GUIDE_MODELS = {"homography": 0, "fundamental": 1}
 
 MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("dist2", "<f4"), ("second2", "<f4")])
 assert MATCH_DTYPE.itemsize == 16
+
+
+class WarpParams(C.Structure):
+    _fields_ = [("out_w", C.c_int32), ("out_h", C.c_int32), ("origin_x", C.c_int32), ("origin_y", C.c_int32), ("fill", C.c_float),
+                ("interp", C.c_uint8), ("path", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+WARP_INTERP = {"nearest": 0, "bilinear": 1}
 
 
 class RansacParams(C.Structure):
@@ -237,5 +246,7 @@ def load():
     # out: host or device memory
     L.sift_hip_result_localize.argtypes = [vp, ci, ci, vp, cs, ci]
     L.sift_hip_localize_points.argtypes = [vp, fp, ci, ci, ci, u16p, u16p, u16p, ci, ci, vp, cs, ci]
+    # imgs, models, out and mask: host or device memory; src and tiles: host arrays or None
+    L.sift_hip_warp_homography.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, C.POINTER(WarpParams), vp, vp, vp, cs, ci]
     _lib = L
     return L

@@ -5,6 +5,7 @@ overlay :59-76) on top of the GPU path — SURVEY.md §8(f) rows 1-3.
     python -m sift_amd.cli -i a.pgm --match b.pgm [--ratio 0.8] [--cross-check]      (an extension: matches.txt)
     python -m sift_amd.cli -i a.pgm --match b.pgm --u8 [--verify ...]                (8-bit descriptors, integer distances)
     python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--iterations 2048] [--threshold 3] [--seed 0] [--refine 0] [--model homography|fundamental] [--refit N] [--localize]   (... and inliers.txt)
+    python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--refine N] --warp out.png   (... and b registered onto a: the homography warp)
     python -m sift_amd.cli -i a.pgm --match b.pgm --verify --guided [--guided-ratio R]   (... and guided.txt: the matches again, under the verified model)
 
 Image ingest follows Vigra's scalar import: band 0 of multi-band files, values unscaled.  PGM,
@@ -153,6 +154,9 @@ def main(argv=None) -> int:
     ap.add_argument("--guided-u8", action="store_true",
                     help="with --verify: --guided by the 8-bit guided matcher (descriptors quantised to 8 bits, integer distances)")
     ap.add_argument("--guided-ratio", type=float, default=None, help="ratio test of --guided / --guided-u8 (default: --ratio)")
+    ap.add_argument("--warp", metavar="PNG",
+                    help="with --verify (a homography): IMG2 resampled onto the image's pixel grid under the verified model, written as PNG "
+                         "(grey replicated to three channels, values rounded and clamped to 0 .. 255; black where IMG2 does not reach)")
     ap.add_argument("--u8", action="store_true",
                     help="with --match: quantise the descriptors to 8 bits on the GPU and match by the integer distance (the distances "
                          "in matches.txt are integers)")
@@ -165,6 +169,8 @@ def main(argv=None) -> int:
         ap.error("--guided needs --verify")
     if args.u8 and not args.match:
         ap.error("--u8 needs --match")
+    if args.warp and not (args.verify and args.model == "homography"):
+        ap.error("--warp needs --verify with --model homography")
     if args.u8 and args.guided:
         ap.error("--u8 cannot be combined with --guided: guided matching takes float descriptors only")
     if args.guided_u8 and not args.verify:
@@ -230,6 +236,12 @@ def main(argv=None) -> int:
                 else:
                     for r in range(3):
                         print("H " + " ".join("%.9g" % float(v) for v in model["h"][3 * r:3 * r + 3]))
+                if args.warp:   # no winner: the all-zero model covers nothing, the picture is black
+                    h, w = np.asarray(img).shape
+                    reg, cover = sift.ctx.warp_homography(read_image(args.match)[None], np.asarray(model["h"], np.float32)[None], out_shape=(h, w), mask=True)
+                    grey = np.clip(np.rint(reg[0]), 0, 255).astype(np.uint8)
+                    _err_call(_lib.load().sift_hip_png_write_bgr8, args.warp.encode(), np.ascontiguousarray(np.repeat(grey[:, :, None], 3, axis=2)).reshape(-1), w, h)
+                    print(f"{args.match} registered -> {args.warp} ({int(cover.sum())} of {w * h} pixels covered)")
                 if args.guided or args.guided_u8:   # no winner: the all-zero model admits nothing, the file is empty
                     ratio = args.ratio if args.guided_ratio is None else args.guided_ratio
                     guided = sift.match_guided(points, points2, model, args.threshold, ratio, args.cross_check, localized,

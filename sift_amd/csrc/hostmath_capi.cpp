@@ -13,6 +13,7 @@
 #include "ransac_refine_math.h"
 #include "ransac_fund_refine_math.h"
 #include "localize_math.h"
+#include "warp_math.h"
 #include "../../include/sift_hip.h"   // sift_hip_homography, sift_hip_fundamental
 
 extern "C" {
@@ -635,5 +636,27 @@ void hostmath_localize(const float* dogs, int L, int w, int h, const uint16_t* x
                 for (int a = -1; a <= 1; ++a) s[9 * (c + 1) + 3 * (b + 1) + (a + 1)] = dogs[(size_t)(i + c) * px + (size_t)(y + b) * (size_t)w + (size_t)(x + a)];
     };
     for (int k = 0; k < m; ++k) out[k] = localize_point(fetch, w, h, L, xs[k], ys[k], is[k], max_moves, octave, coord_scale);
+}
+}
+
+// ---- homography warp (warp_math.h): the plain loop ---------------------------------------------------------------
+extern "C" {
+// job j: image src[j] (src null: image j) of imgs (w x h each) under models[9 j ..] -> out[j] (out_h x out_w) and, unless null, mask[j]
+void hostmath_warp_homography(const float* imgs, int w, int h, int n_jobs, const int32_t* src, const float* models, const sift_hip_warp_params* p,
+                              float* out, uint8_t* mask) {
+    using namespace sift_hip;
+    const size_t px = (size_t)p->out_w * (size_t)p->out_h;
+    for (int j = 0; j < n_jobs; ++j) {
+        const float* s = imgs + (size_t)(src ? src[j] : j) * (size_t)w * (size_t)h;
+        float m[9];
+        for (int k = 0; k < 9; ++k) m[k] = models[9 * (size_t)j + k];
+        for (int y = 0; y < p->out_h; ++y)
+            for (int x = 0; x < p->out_w; ++x) {
+                uint8_t covered;
+                const size_t o = (size_t)j * px + (size_t)y * (size_t)p->out_w + (size_t)x;
+                out[o] = warp_pixel(s, w, h, m, x, y, p->origin_x, p->origin_y, p->fill, p->interp, covered);
+                if (mask) mask[o] = covered;
+            }
+    }
 }
 }

@@ -868,6 +868,51 @@ class Context:
             _raise(rc, err)
         return recs[:total.value], counts, models, inlier[:total.value]
 
+    # ---- homography warp (include/sift_hip.h, "homography warp") ---------------------------------------------
+    def warp_homography(self, imgs, models, src=None, out_shape=None, origin=(0, 0), fill=0.0, interp="bilinear", path=0, out=None, mask=False,
+                        want_tiles=False, shape=None):
+        """sift_hip_warp_homography: job j resamples image src[j] (None: image j) under models[j] -> (out[, mask][, tiles]):
+        out [n_jobs, out_h, out_w] float32, pixel (x, y) being the source at H (x + origin[0], y + origin[1], 1); mask one byte
+        per pixel (1: covered, else `fill`); tiles = (staged, direct) with `want_tiles`.  The model maps query to train, so the
+        H of a verified pair brings the pair's TRAIN image into its QUERY frame.  `imgs`: a numpy array [n, h, w], or a tensor
+        / an address (device memory) with `shape` = (n, h, w); `models`: [n_jobs, 9] numbers, the records verify_images returns,
+        a tensor or an address; `out_shape` (h, w): the images' by default; `interp`: "nearest" or "bilinear"; `path` 1: every
+        tile reads global memory (the same bits); `out`, and `mask` when it is not a bool: where a result goes (returned as given)."""
+        if isinstance(imgs, np.ndarray):
+            imgs = np.ascontiguousarray(imgs, np.float32)
+            imgs = imgs[None] if imgs.ndim == 2 else imgs
+            shape = imgs.shape
+        elif shape is None:
+            shape = tuple(imgs.shape)   # a tensor
+        if len(shape) != 3:
+            raise ValueError("warp_homography: imgs is [n, h, w]")
+        if interp not in _lib.WARP_INTERP:
+            raise ValueError('warp_homography: interp must be "nearest" or "bilinear"')
+        if isinstance(models, np.ndarray) and models.dtype.names:
+            models = models["h"]
+        if isinstance(models, (np.ndarray, list, tuple)):
+            models = np.ascontiguousarray(models, np.float32).reshape(-1, 9)
+            n_jobs = models.shape[0]
+        else:
+            n_jobs = len(src) if src is not None else int(shape[0])
+        if src is not None:
+            src = np.ascontiguousarray(src, np.int32).reshape(-1)
+            if src.size != n_jobs:
+                raise ValueError("warp_homography: one src index per model")
+        oh, ow = (int(shape[1]), int(shape[2])) if out_shape is None else (int(out_shape[0]), int(out_shape[1]))
+        prm = _lib.WarpParams(ow, oh, int(origin[0]), int(origin[1]), float(fill), _lib.WARP_INTERP[interp], int(path) & 0xff)
+        size = (n_jobs, max(oh, 0), max(ow, 0))   # a bad size: the call says so
+        res = np.zeros(size, np.float32) if out is None else out
+        msk = (np.zeros(size, np.uint8) if mask else None) if isinstance(mask, bool) else mask
+        tiles = np.zeros(2, np.int64) if want_tiles else None
+        err = C.create_string_buffer(512)
+        rc = self._L.sift_hip_warp_homography(self._h, self._addr(imgs), int(shape[0]), int(shape[2]), int(shape[1]), n_jobs, self._addr(src),
+                                              self._addr(models), C.byref(prm), self._addr(res), self._addr(msk), self._addr(tiles), err, 512)
+        if rc:
+            _raise(rc, err)
+        got = (res,) + ((msk,) if msk is not None else ()) + (((int(tiles[0]), int(tiles[1])),) if want_tiles else ())
+        return got[0] if len(got) == 1 else got
+
 
 class Group:
     """sift_hip_group: one batch block-sharded over several GPUs of this node from one process (one context and host thread
@@ -1081,6 +1126,23 @@ class Sift:
         run = self.ctx.ransac_fundamental if model == "fundamental" else self.ctx.ransac_homography
         models, inlier = run(pts, None, iterations, threshold, seed, refine=refine)
         return recs, models[0], inlier
+
+    def register(self, imgs, pairs, ratio: float = 0.8, cross_check: bool = False, iterations: int = 2048, threshold: float = 3.0, seed: int = 0,
+                 refine: int = 0, quantized: bool = False, fill: float = 0.0, interp: str = "bilinear"):
+        """Registration (an extension): calculate() on every frame of `imgs` [n, h, w], verify() on every pair (query, train) and
+        Context.warp_homography of each pair's train frame into its query frame -> (models, registered, mask): one homography
+        record per pair, registered[p] the train frame resampled on the query frame's pixels, mask[p] 1 where it is covered
+        (elsewhere `fill`; a pair without a model is all `fill`).  Bit for bit the composition of those calls."""
+        imgs = np.asarray(imgs)
+        if imgs.ndim != 3:
+            raise ValueError("register: imgs is [n, h, w]")
+        pairs = [(int(q), int(t)) for q, t in pairs]
+        points = [self.calculate(img) for img in imgs]
+        models = np.zeros(len(pairs), _lib.HOMOGRAPHY_DTYPE)
+        for p, (q, t) in enumerate(pairs):
+            models[p] = self.verify(points[q], points[t], ratio, cross_check, iterations, threshold, seed, refine, "homography", quantized)[1]
+        registered, mask = self.ctx.warp_homography(imgs.astype(np.float32), models, [t for _, t in pairs], fill=fill, interp=interp, mask=True)
+        return models, registered, mask
 
     def refine_fundamental(self, points_a, points_b, recs, model, threshold: float = 3.0, rounds: int = 2, localized=None):
         """The least-squares refit of the record verify(model="fundamental") returned, over its own inliers among `recs` (an
