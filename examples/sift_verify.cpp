@@ -3,8 +3,9 @@
 // or, with model=fundamental, sift::Matcher::verify_fundamental(): a seven-point fundamental matrix, the model for two views of a
 // general scene.  inliers.txt holds the lines of matches.txt that agree with the model.
 //   g++ -std=c++17 -pthread -Iinclude examples/sift_verify.cpp -Lsift_amd/lib -lsift_hip -Wl,-rpath,$PWD/sift_amd/lib -o sift_verify
-//   ./sift_verify a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [refine=0] [model=homography|fundamental] [refit=-1] [localize=0] [warp out.pgm]
+//   ./sift_verify a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [refine=0] [model=homography|fundamental] [refit=-1] [localize=0] [warp|mosaic out.pgm]
 //   ... warp out.pgm (with model=homography): b registered onto a under the verified model (sift::Matcher::warp), as an 8-bit PGM
+//   ... mosaic out.pgm (likewise; a and b of one size): both frames feathered on the canvas that holds them (sift::Matcher::composite)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -39,7 +40,7 @@ static void write_matches(const char* path, const std::vector<sift::Match>& matc
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::cerr << "usage: " << argv[0]
-                  << " a.{pgm,ppm,png,jpg} b.{...} [octaves] [dogsPerEpoch] [ratio] [crossCheck] [iterations] [threshold] [seed] [refine] [homography|fundamental] [refit] [localize] [warp out.pgm]\n";
+                  << " a.{pgm,ppm,png,jpg} b.{...} [octaves] [dogsPerEpoch] [ratio] [crossCheck] [iterations] [threshold] [seed] [refine] [homography|fundamental] [refit] [localize] [warp|mosaic out.pgm]\n";
         return 1;
     }
     const u16_t octaves = argc > 3 ? (u16_t)std::atoi(argv[3]) : 4;
@@ -61,8 +62,10 @@ int main(int argc, char** argv) {
     const bool localize = argc > 13 && std::atoi(argv[13]) != 0;
     // "warp out.pgm": b resampled on a's pixel grid under the verified homography
     const std::string warp_file = argc > 15 && std::string(argv[14]) == "warp" ? argv[15] : "";
-    if (!warp_file.empty() && model_name != "homography") {
-        std::cerr << "warp is for model=homography\n";
+    // "mosaic out.pgm": a under the identity and b under the verified homography on one canvas
+    const std::string mosaic_file = argc > 15 && std::string(argv[14]) == "mosaic" ? argv[15] : "";
+    if ((!warp_file.empty() || !mosaic_file.empty()) && model_name != "homography") {
+        std::cerr << "warp and mosaic are for model=homography\n";
         return 1;
     }
     if (refit >= 0 && model_name != "fundamental") {
@@ -128,6 +131,47 @@ int main(int argc, char** argv) {
             }
             std::fclose(out);
             std::cout << argv[2] << " registered -> " << warp_file << "\n";
+        }
+        if (!mosaic_file.empty()) {   // no homography: the all-zero model covers nothing, the picture is a alone
+            char err[512] = "";
+            int w = 0, h = 0, wb = 0, hb = 0;
+            if (sift_hip_image_info(argv[1], &w, &h, nullptr, nullptr, err, sizeof(err)) != SIFT_HIP_OK ||
+                sift_hip_image_info(argv[2], &wb, &hb, nullptr, nullptr, err, sizeof(err)) != SIFT_HIP_OK)
+                throw std::runtime_error(err);
+            if (w != wb || h != hb) throw std::runtime_error("mosaic: the two images must have one size");
+            sift::Image2f fa(w, h), fb(w, h);
+            if (sift_hip_image_read_band0(argv[1], fa.data(), (long long)w * h, err, sizeof(err)) != SIFT_HIP_OK ||
+                sift_hip_image_read_band0(argv[2], fb.data(), (long long)w * h, err, sizeof(err)) != SIFT_HIP_OK)
+                throw std::runtime_error(err);
+            // the canvas: a's frame and b's corners through the inverse model (adjugate, double), at most 4 x the larger side around a
+            const double reach = 4.0 * std::max(w, h);
+            double m[9], x0 = 0, y0 = 0, x1 = w - 1, y1 = h - 1;
+            for (int k = 0; k < 9; ++k) m[k] = (double)model.h[k];
+            const double adj[9] = {m[4] * m[8] - m[5] * m[7], m[2] * m[7] - m[1] * m[8], m[1] * m[5] - m[2] * m[4],
+                                   m[5] * m[6] - m[3] * m[8], m[0] * m[8] - m[2] * m[6], m[2] * m[3] - m[0] * m[5],
+                                   m[3] * m[7] - m[4] * m[6], m[1] * m[6] - m[0] * m[7], m[0] * m[4] - m[1] * m[3]};
+            for (int c = 0; c < 4 && model.iteration >= 0; ++c) {
+                const double u = (c & 1) ? w - 1 : 0, v = (c & 2) ? h - 1 : 0, W = adj[6] * u + adj[7] * v + adj[8];
+                const double x = (adj[0] * u + adj[1] * v + adj[2]) / W, y = (adj[3] * u + adj[4] * v + adj[5]) / W;
+                if (!(std::isfinite(x) && std::isfinite(y))) continue;
+                x0 = std::min(x0, std::floor(x)); x1 = std::max(x1, std::ceil(x));
+                y0 = std::min(y0, std::floor(y)); y1 = std::max(y1, std::ceil(y));
+            }
+            x0 = std::max(x0, -reach); y0 = std::max(y0, -reach);
+            x1 = std::min(x1, w - 1 + reach); y1 = std::min(y1, h - 1 + reach);
+            const int cw = (int)(x1 - x0) + 1, ch = (int)(y1 - y0) + 1;
+            std::array<f32_t, 9> ident = {1, 0, 0, 0, 1, 0, 0, 0, 1}, hb9;
+            std::copy(model.h, model.h + 9, hb9.begin());
+            sift::Image2f pic = matcher.composite({&fa, &fb}, {ident, hb9}, cw, ch, (int)x0, (int)y0);
+            FILE* out = std::fopen(mosaic_file.c_str(), "wb");
+            if (!out) throw std::runtime_error("cannot write " + mosaic_file);
+            std::fprintf(out, "P5\n%d %d\n255\n", cw, ch);
+            for (size_t i = 0; i < (size_t)cw * (size_t)ch; ++i) {
+                const float v = std::nearbyint(pic.data()[i]);
+                std::fputc((int)(v < 0.0f ? 0.0f : v > 255.0f ? 255.0f : v), out);
+            }
+            std::fclose(out);
+            std::cout << argv[1] << " + " << argv[2] << " -> " << mosaic_file << " (" << cw << " x " << ch << ", origin " << (int)x0 << ", " << (int)y0 << ")\n";
         }
     } catch (std::exception& ex) {
         std::cerr << ex.what() << std::endl;

@@ -3,6 +3,8 @@
 // squared distances on the GPU's f32 matrix cores, the two nearest rows of every query point, ratio test, cross-check.
 #ifndef SIFT_AMD_MATCH_HPP
 #define SIFT_AMD_MATCH_HPP
+#include <algorithm>
+#include <array>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -205,6 +207,40 @@ public:
         char err[512] = "";
         const int rc = sift_hip_warp_homography(_ctx, train.data(), 1, (int)train.width(), (int)train.height(), 1, nullptr, h, &prm, out.data(),
                                                 covered ? covered->data() : nullptr, nullptr, err, sizeof(err));
+        if (rc == SIFT_HIP_EINVAL) throw std::invalid_argument(err);
+        if (rc != SIFT_HIP_OK) throw std::runtime_error(err);
+        return out;
+    }
+
+    // The compositor (include/sift_hip.h, "compositor"): `frames` (all of one size) accumulated in order on ONE out_w x out_h
+    // canvas, frame k under the nine floats models[k] (canvas lattice -> frame, as warp() takes them; the reference frame's is
+    // the identity); canvas pixel (x, y) is the lattice point (x + origin_x, y + origin_y).  blend: 0 the first covering
+    // frame's value, 1 the mean, 2 feathered by the distance to each frame's border.  Where no frame reaches: `fill`, and 0 in
+    // *count (may be null; else the number of covering frames per pixel).  Throws std::invalid_argument for what
+    // sift_hip_composite_homography rejects.
+    Image2f composite(const std::vector<Image2f*>& frames, const std::vector<std::array<f32_t, 9>>& models, int out_w, int out_h, int origin_x = 0,
+                      int origin_y = 0, int blend = 2, f32_t fill = 0.0f, bool bilinear = true, std::vector<uint16_t>* count = nullptr) {
+        if (frames.empty() || frames.size() != models.size()) throw std::invalid_argument("composite: one model per frame, at least one frame");
+        const size_t w = frames[0]->width(), h = frames[0]->height();
+        std::vector<f32_t> stack(frames.size() * w * h);
+        for (size_t k = 0; k < frames.size(); ++k) {
+            if (frames[k]->width() != w || frames[k]->height() != h) throw std::invalid_argument("composite: frames of one size");
+            std::copy(frames[k]->data(), frames[k]->data() + w * h, stack.begin() + k * w * h);
+        }
+        sift_hip_composite_params prm{};
+        prm.out_w = out_w;
+        prm.out_h = out_h;
+        prm.origin_x = origin_x;
+        prm.origin_y = origin_y;
+        prm.fill = fill;
+        prm.interp = bilinear ? 1 : 0;
+        prm.blend = (uint8_t)blend;
+        Image2f out(out_w > 0 ? out_w : 0, out_h > 0 ? out_h : 0);
+        if (count) count->assign((size_t)out.width() * (size_t)out.height(), 0);
+        const int64_t offsets[2] = {0, (int64_t)frames.size()};
+        char err[512] = "";
+        const int rc = sift_hip_composite_homography(_ctx, stack.data(), (int)frames.size(), (int)w, (int)h, 1, offsets, nullptr, models[0].data(), &prm,
+                                                     out.data(), count ? count->data() : nullptr, nullptr, err, sizeof(err));
         if (rc == SIFT_HIP_EINVAL) throw std::invalid_argument(err);
         if (rc != SIFT_HIP_OK) throw std::runtime_error(err);
         return out;

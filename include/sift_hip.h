@@ -576,6 +576,40 @@ int sift_hip_warp_homography(sift_hip_ctx* ctx, const float* imgs, int n_imgs, i
                              const float* models, const sift_hip_warp_params* params, float* out, uint8_t* mask, int64_t* tiles,
                              char* err, int errlen);
 
+/* ---- compositor (an extension) -----------------------------------------------------------------------------
+ * Many frames in one picture: canvas c accumulates the jobs j = offsets[c] .. offsets[c + 1] - 1, IN THAT ORDER, each job an
+ * image src[j] under the nine floats models[9 j ..] as in the homography warp, into out[c] (out_h x out_w) - a panorama on a
+ * canvas larger than any frame, or a burst stacked on its reference frame's lattice.  One launch for all canvases; every canvas
+ * pixel is written once.  sift_amd/csrc/composite_math.h defines every bit on top of warp_math.h (the map, the coverage test,
+ * the taps and the interpolation are the warp's own functions); the kernel and a plain host loop
+ * (hostmath_composite_homography) compile it.  For canvas pixel (x, y): acc = wsum = +0.0f, cnt = 0; for each job in order
+ * that covers the lattice point (x + origin_x, y + origin_y) - the warp's test - with val the warp's value there: cnt += 1 and
+ *   blend 0 (first)    the first covering job's val is kept, later jobs only count           -> val
+ *   blend 1 (mean)     acc = acc + val                                                       -> acc / (float)cnt
+ *   blend 2 (feather)  wgt = fminf(fminf(u, (float)(w - 1) - u), fminf(v, (float)(h - 1) - v)) + 1.0f (the distance to the
+ *                      source frame's border plus one), acc = fmaf(wgt, val, acc), wsum = wsum + wgt   -> acc / wsum
+ * cnt == 0: fill.  count (may be NULL) receives cnt.  The quotients are correctly rounded.  The result does not depend on
+ * `path`, tiles, culling or the launch: it is bit for bit the host loop's. */
+typedef struct sift_hip_composite_params {
+    int32_t out_w, out_h;        /* > 0 */
+    int32_t origin_x, origin_y;  /* canvas pixel (x, y) is the lattice point (x + origin_x, y + origin_y) of the models' query frame */
+    float fill;
+    uint8_t interp;              /* 0 nearest, 1 bilinear; above: EINVAL */
+    uint8_t blend;               /* 0 first, 1 mean, 2 feather; above: EINVAL */
+    uint8_t path;                /* 0: the library chooses per tile and job; 1: every tap from global memory (same bits; measurement and tests) */
+    uint8_t reserved;            /* zero */
+} sift_hip_composite_params;     /* 24 bytes */
+/* imgs (n_imgs x h x w), models (n_jobs x 9, n_jobs = offsets[n_canvases]), out (n_canvases x out_h x out_w) and count (same
+ * shape, uint16; may be NULL) may each be host or device memory; offsets (host, n_canvases + 1), src (host; NULL: job j reads
+ * image j) and tiles (host, may be NULL: (tile, job) visits [0] whose source footprint was staged in LDS, [1] whose taps were
+ * read directly, [2] skipped because no pixel of the tile was covered).  A canvas without jobs is all fill, count 0.  Scratch
+ * memory, stream and "not while a batch is in flight" as for sift_hip_warp_homography.  SIFT_HIP_EINVAL for the warp's size
+ * limits, a bad interp, blend, path or src index, a non-zero reserved byte, offsets that do not start at 0 or decrease, more
+ * than 65535 canvases or more than 65535 jobs in one canvas. */
+int sift_hip_composite_homography(sift_hip_ctx* ctx, const float* imgs, int n_imgs, int w, int h, int n_canvases, const int64_t* offsets,
+                                  const int32_t* src, const float* models, const sift_hip_composite_params* params, float* out,
+                                  uint16_t* count, int64_t* tiles, char* err, int errlen);
+
 /* ---- inspection of the last batch (parity tests) ------------------------------------------------ */
 /* kind: 0 gaussian (levels 0..D), 1 dog (0..D-1), 2 magnitude, 3 orientation (initial gradient
  * maps, sift.cpp:130-160, only for levels some keypoint scale selects; 0x0 otherwise). */

@@ -43,7 +43,7 @@ SYMBOLS = [
     "sift_hip_quantize", "sift_hip_result_copy_u8", "sift_hip_knn2_u8", "sift_hip_match_u8",
     "sift_hip_knn2_guided_u8", "sift_hip_match_guided_u8", "sift_hip_result_match_guided_u8",
     "sift_hip_result_localize", "sift_hip_localize_points",
-    "sift_hip_warp_homography",
+    "sift_hip_warp_homography", "sift_hip_composite_homography",
 ]
 
 
@@ -72,6 +72,14 @@ class WarpParams(C.Structure):
 
 
 WARP_INTERP = {"nearest": 0, "bilinear": 1}
+
+
+class CompositeParams(C.Structure):
+    _fields_ = [("out_w", C.c_int32), ("out_h", C.c_int32), ("origin_x", C.c_int32), ("origin_y", C.c_int32), ("fill", C.c_float),
+                ("interp", C.c_uint8), ("blend", C.c_uint8), ("path", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+COMPOSITE_BLEND = {"first": 0, "mean": 1, "feather": 2}
 
 
 class RansacParams(C.Structure):
@@ -248,5 +256,7 @@ def load():
     L.sift_hip_localize_points.argtypes = [vp, fp, ci, ci, ci, u16p, u16p, u16p, ci, ci, vp, cs, ci]
     # imgs, models, out and mask: host or device memory; src and tiles: host arrays or None
     L.sift_hip_warp_homography.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, C.POINTER(WarpParams), vp, vp, vp, cs, ci]
+    # imgs, models, out and count: host or device memory; offsets, src and tiles: host arrays (src, tiles: or None)
+    L.sift_hip_composite_homography.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, C.POINTER(CompositeParams), vp, vp, vp, cs, ci]
     _lib = L
     return L

@@ -22,6 +22,7 @@
 #include "match_kernels.h"
 #include "ransac_kernels.h"
 #include "warp_kernels.h"
+#include "composite_kernels.h"
 
 using namespace sift_hip;
 
@@ -210,6 +211,7 @@ struct sift_hip_ctx {
     sift_hip::MatchState* match_state = nullptr;   // the matcher's scratch (match.cpp), made by the first match call
     sift_hip::RansacState* ransac_state = nullptr; // the same for the geometric verification (ransac.cpp)
     sift_hip::WarpState* warp_state = nullptr;     // the same for the homography warp (warp.cpp)
+    sift_hip::CompositeState* composite_state = nullptr;   // the same for the compositor (composite.cpp)
     // sub-pixel localisation (sift_hip_result_localize): the records and their (x, y) of the last batch, the images' row offsets
     DevBuf d_loc, d_loc_xy, d_loc_row0;
     HostBuf h_loc_row0;               // page-locked image of the row offsets (every call ends in a wait, so it is free again)
@@ -1301,6 +1303,7 @@ int match_guarded(char* err, int errlen, int (*fn)(void*), void* arg) { return g
 void match_set_err(char* err, int errlen, const char* msg) { set_err(err, errlen, msg); }
 RansacState** ransac_ctx_state(sift_hip_ctx* c) { return &c->ransac_state; }
 WarpState** warp_ctx_state(sift_hip_ctx* c) { return &c->warp_state; }
+CompositeState** composite_ctx_state(sift_hip_ctx* c) { return &c->composite_state; }
 bool ransac_ctx_subpixel(sift_hip_ctx* c) { return c->plan.params.subpixel != 0; }
 const float* localize_ctx_xy(sift_hip_ctx* c) { return (c->have_result && c->loc_use) ? c->d_loc_xy.as<float>() : nullptr; }
 }  // namespace sift_hip
@@ -1353,6 +1356,7 @@ int sift_hip_create(int device, sift_hip_ctx** out, char* err, int errlen) {
                 tu_touch_match(c->stream);
                 tu_touch_localize(c->stream);
                 tu_touch_warp(c->stream);
+                tu_touch_composite(c->stream);
                 SIFT_HIP_CHECK(hipGetLastError());
                 SIFT_HIP_CHECK(hipStreamSynchronize(c->stream));
                 touched[device] = true;
@@ -1371,6 +1375,7 @@ void sift_hip_destroy(sift_hip_ctx* c) {
     match_state_free(c->match_state);
     ransac_state_free(c->ransac_state);
     warp_state_free(c->warp_state);
+    composite_state_free(c->composite_state);
     ApiGuard api;
     for (DevBuf* b : {&c->arena, &c->d_plan, &c->d_taps, &c->d_luts, &c->d_taps16, &c->d_input, &c->d_input_u8, &c->d_sparse_rec, &c->d_sparse_val, &c->d_base, &c->d_tmp, &c->d_tmp2,
                       &c->d_wk, &c->d_wi, &c->d_wi2, &c->d_wp, &c->d_status, &c->d_pool, &c->d_order, &c->d_masks, &c->d_fmasks, &c->d_counts, &c->d_tile_counts, &c->d_totals, &c->d_cands, &c->d_flags, &c->d_list, &c->d_list_cnt, &c->d_orient,

@@ -14,6 +14,7 @@
 #include "ransac_fund_refine_math.h"
 #include "localize_math.h"
 #include "warp_math.h"
+#include "composite_math.h"
 #include "../../include/sift_hip.h"   // sift_hip_homography, sift_hip_fundamental
 
 extern "C" {
@@ -658,5 +659,24 @@ void hostmath_warp_homography(const float* imgs, int w, int h, int n_jobs, const
                 if (mask) mask[o] = covered;
             }
     }
+}
+}
+
+// ---- compositor (composite_math.h): the plain loop ---------------------------------------------------------------
+extern "C" {
+// canvas c: jobs offsets[c] .. offsets[c + 1] - 1 in order (job j reads image src[j]; src null: image j) -> out[c] (out_h x out_w)
+// and, unless null, count[c]
+void hostmath_composite_homography(const float* imgs, int w, int h, int n_canvases, const int64_t* offsets, const int32_t* src, const float* models,
+                                   const sift_hip_composite_params* p, float* out, uint16_t* count) {
+    using namespace sift_hip;
+    const size_t px = (size_t)p->out_w * (size_t)p->out_h;
+    for (int c = 0; c < n_canvases; ++c)
+        for (int y = 0; y < p->out_h; ++y)
+            for (int x = 0; x < p->out_w; ++x) {
+                uint16_t cnt;
+                const size_t o = (size_t)c * px + (size_t)y * (size_t)p->out_w + (size_t)x;
+                out[o] = composite_pixel(imgs, w, h, src, models, offsets[c], offsets[c + 1], x, y, p->origin_x, p->origin_y, p->fill, p->interp, p->blend, cnt);
+                if (count) count[o] = cnt;
+            }
 }
 }

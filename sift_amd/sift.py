@@ -913,6 +913,56 @@ class Context:
         got = (res,) + ((msk,) if msk is not None else ()) + (((int(tiles[0]), int(tiles[1])),) if want_tiles else ())
         return got[0] if len(got) == 1 else got
 
+    # ---- compositor (include/sift_hip.h, "compositor") ---------------------------------------------------------
+    def composite_homography(self, imgs, models, offsets=None, src=None, out_shape=None, origin=(0, 0), fill=0.0, interp="bilinear", blend="feather",
+                             path=0, out=None, count=False, want_tiles=False, shape=None):
+        """sift_hip_composite_homography: canvas c accumulates jobs offsets[c] .. offsets[c + 1] - 1 in order, job j being image
+        src[j] (None: image j) under models[j] as in warp_homography -> (out[, count][, tiles]): out [n_canvases, out_h, out_w]
+        float32, one picture per canvas; count uint16, the jobs that cover each pixel (0: `fill`); tiles = (staged, direct,
+        skipped) (tile, job) visits with `want_tiles`.  `offsets` None: one canvas of all jobs.  `blend`: "first" (the first
+        covering job's value), "mean" or "feather" (weights: distance to the source frame's border plus one).  `imgs`, `models`,
+        `out_shape`, `origin`, `interp`, `path`, `shape` as in warp_homography; `out`, and `count` when it is not a bool: where
+        a result goes (returned as given)."""
+        if isinstance(imgs, np.ndarray):
+            imgs = np.ascontiguousarray(imgs, np.float32)
+            imgs = imgs[None] if imgs.ndim == 2 else imgs
+            shape = imgs.shape
+        elif shape is None:
+            shape = tuple(imgs.shape)   # a tensor
+        if len(shape) != 3:
+            raise ValueError("composite_homography: imgs is [n, h, w]")
+        if interp not in _lib.WARP_INTERP:
+            raise ValueError('composite_homography: interp must be "nearest" or "bilinear"')
+        if blend not in _lib.COMPOSITE_BLEND:
+            raise ValueError('composite_homography: blend must be "first", "mean" or "feather"')
+        if isinstance(models, np.ndarray) and models.dtype.names:
+            models = models["h"]
+        if isinstance(models, (np.ndarray, list, tuple)):
+            models = np.ascontiguousarray(models, np.float32).reshape(-1, 9)
+            n_jobs = models.shape[0]
+        else:
+            n_jobs = len(src) if src is not None else int(shape[0])
+        if src is not None:
+            src = np.ascontiguousarray(src, np.int32).reshape(-1)
+            if src.size != n_jobs:
+                raise ValueError("composite_homography: one src index per model")
+        offsets = np.array([0, n_jobs], np.int64) if offsets is None else np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        if offsets.size < 1 or offsets[-1] != n_jobs:
+            raise ValueError("composite_homography: offsets has one entry per canvas and one more, the last being the number of models")
+        oh, ow = (int(shape[1]), int(shape[2])) if out_shape is None else (int(out_shape[0]), int(out_shape[1]))
+        prm = _lib.CompositeParams(ow, oh, int(origin[0]), int(origin[1]), float(fill), _lib.WARP_INTERP[interp], _lib.COMPOSITE_BLEND[blend], int(path) & 0xff)
+        size = (offsets.size - 1, max(oh, 0), max(ow, 0))   # a bad size: the call says so
+        res = np.zeros(size, np.float32) if out is None else out
+        cnt = (np.zeros(size, np.uint16) if count else None) if isinstance(count, bool) else count
+        tiles = np.zeros(3, np.int64) if want_tiles else None
+        err = C.create_string_buffer(512)
+        rc = self._L.sift_hip_composite_homography(self._h, self._addr(imgs), int(shape[0]), int(shape[2]), int(shape[1]), offsets.size - 1, self._addr(offsets),
+                                                   self._addr(src), self._addr(models), C.byref(prm), self._addr(res), self._addr(cnt), self._addr(tiles), err, 512)
+        if rc:
+            _raise(rc, err)
+        got = (res,) + ((cnt,) if cnt is not None else ()) + ((tuple(int(t) for t in tiles),) if want_tiles else ())
+        return got[0] if len(got) == 1 else got
+
 
 class Group:
     """sift_hip_group: one batch block-sharded over several GPUs of this node from one process (one context and host thread
@@ -1143,6 +1193,67 @@ class Sift:
             models[p] = self.verify(points[q], points[t], ratio, cross_check, iterations, threshold, seed, refine, "homography", quantized)[1]
         registered, mask = self.ctx.warp_homography(imgs.astype(np.float32), models, [t for _, t in pairs], fill=fill, interp=interp, mask=True)
         return models, registered, mask
+
+    @staticmethod
+    def mosaic_canvas(models, w: int, h: int):
+        """The canvas mosaic() chooses -> (origin (x, y), shape (out_h, out_w)): in float64, the box of the w x h reference frame
+        and of every model's frame corners through the inverse model, each side clipped to 4 x the frame's larger side around
+        the reference frame (a frame with a corner at or behind the horizon reaches as far as allowed)."""
+        reach = 4 * max(w, h)
+        lo, hi = np.array([-reach, -reach], np.float64), np.array([w - 1 + reach, h - 1 + reach], np.float64)
+        box_lo, box_hi = np.zeros(2), np.array([w - 1, h - 1], np.float64)
+        corners = np.array([[0, 0, 1], [w - 1, 0, 1], [0, h - 1, 1], [w - 1, h - 1, 1]], np.float64).T
+        for m in np.asarray(models, np.float64).reshape(-1, 3, 3):
+            with np.errstate(all="ignore"):
+                c = np.linalg.inv(m) @ corners if abs(np.linalg.det(m)) > 0 else np.full((3, 4), np.nan)
+                xy = c[:2] / c[2]
+            if not (np.isfinite(xy).all() and (c[2] * c[2, 0] > 0).all()):
+                box_lo, box_hi = lo.copy(), hi.copy()
+                continue
+            box_lo, box_hi = np.minimum(box_lo, np.floor(xy.min(axis=1))), np.maximum(box_hi, np.ceil(xy.max(axis=1)))
+        box_lo, box_hi = np.clip(box_lo, lo, hi), np.clip(box_hi, lo, hi)
+        return (int(box_lo[0]), int(box_lo[1])), (int(box_hi[1] - box_lo[1]) + 1, int(box_hi[0] - box_lo[0]) + 1)
+
+    def mosaic(self, imgs, ref: int = 0, pairs=None, blend: str = "feather", ratio: float = 0.8, cross_check: bool = False, iterations: int = 2048,
+               threshold: float = 3.0, seed: int = 0, refine: int = 0, quantized: bool = False, fill: float = 0.0, interp: str = "bilinear",
+               chain: bool = False, canvas=None):
+        """A mosaic or a stack (an extension): calculate() on every frame of `imgs` [n, h, w], verify() on every pair (query,
+        train) and Context.composite_homography of the placed frames on one canvas in frame `ref`'s coordinates -> (models,
+        canvas, count, origin): one homography record per pair, the picture [out_h, out_w], the number of frames that cover each
+        pixel (0: `fill`), and origin (x, y), the lattice point of `ref` at canvas pixel (0, 0).  `pairs`: (ref, k) for every
+        other frame k by default, and every query must be `ref`; with `chain` the pairs are taken in order, each query being
+        `ref` or an earlier pair's train frame, and a frame's model to `ref` is the float64 product along its chain, rounded
+        once to float.  Job 0 is frame `ref` under the identity, then the train frames in the pairs' order; a frame without a
+        model (or behind one in its chain) is left out, and a frame is placed once, by its first pair.  `canvas` None: the box, computed in float64, of every placed frame's
+        corners through its inverse model, each side clipped to 4 x the frame's larger side around frame `ref`; else (origin,
+        shape) = ((x, y), (out_h, out_w)).  Bit for bit the composition of those calls."""
+        imgs = np.asarray(imgs)
+        if imgs.ndim != 3:
+            raise ValueError("mosaic: imgs is [n, h, w]")
+        n, h, w = imgs.shape
+        ref = int(ref)
+        pairs = [(ref, k) for k in range(n) if k != ref] if pairs is None else [(int(q), int(t)) for q, t in pairs]
+        to_ref = {ref: np.eye(3)}   # frame -> the float64 model from ref's lattice to the frame, as far as it is exact
+        for q, t in pairs:
+            if not chain and q != ref:
+                raise ValueError("mosaic: without chain every pair's query is the reference frame")
+        points = [self.calculate(img) for img in imgs]
+        models = np.zeros(len(pairs), _lib.HOMOGRAPHY_DTYPE)
+        job_models, src = [np.eye(3, dtype=np.float32).reshape(9)], [ref]
+        for p, (q, t) in enumerate(pairs):
+            models[p] = self.verify(points[q], points[t], ratio, cross_check, iterations, threshold, seed, refine, "homography", quantized)[1]
+            if models[p]["iteration"] < 0 or q not in to_ref or t in to_ref:
+                continue
+            to_ref[t] = models[p]["h"].astype(np.float64).reshape(3, 3) @ to_ref[q]
+            job_models.append(models[p]["h"] if q == ref else to_ref[t].astype(np.float32).reshape(9))
+            src.append(t)
+        job_models = np.array(job_models, np.float32)
+        if canvas is None:
+            origin, shape = self.mosaic_canvas(job_models[1:], w, h)
+        else:
+            origin, shape = (int(canvas[0][0]), int(canvas[0][1])), (int(canvas[1][0]), int(canvas[1][1]))
+        out, count = self.ctx.composite_homography(imgs.astype(np.float32), job_models, None, src, shape, origin, fill, interp, blend, count=True)
+        return models, out[0], count[0], origin
 
     def refine_fundamental(self, points_a, points_b, recs, model, threshold: float = 3.0, rounds: int = 2, localized=None):
         """The least-squares refit of the record verify(model="fundamental") returned, over its own inliers among `recs` (an
