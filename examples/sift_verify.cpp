@@ -3,9 +3,10 @@
 // or, with model=fundamental, sift::Matcher::verify_fundamental(): a seven-point fundamental matrix, the model for two views of a
 // general scene.  inliers.txt holds the lines of matches.txt that agree with the model.
 //   g++ -std=c++17 -pthread -Iinclude examples/sift_verify.cpp -Lsift_amd/lib -lsift_hip -Wl,-rpath,$PWD/sift_amd/lib -o sift_verify
-//   ./sift_verify a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [refine=0] [model=homography|fundamental] [refit=-1] [localize=0] [warp|mosaic out.pgm]
+//   ./sift_verify a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [refine=0] [model=homography|fundamental] [refit=-1] [localize=0] [warp|mosaic out.pgm [gain]]
 //   ... warp out.pgm (with model=homography): b registered onto a under the verified model (sift::Matcher::warp), as an 8-bit PGM
 //   ... mosaic out.pgm (likewise; a and b of one size): both frames feathered on the canvas that holds them (sift::Matcher::composite)
+//   ... mosaic out.pgm gain: the frames' gains are solved from their overlap first (sift::Matcher::overlap) and applied
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -64,6 +65,7 @@ int main(int argc, char** argv) {
     const std::string warp_file = argc > 15 && std::string(argv[14]) == "warp" ? argv[15] : "";
     // "mosaic out.pgm": a under the identity and b under the verified homography on one canvas
     const std::string mosaic_file = argc > 15 && std::string(argv[14]) == "mosaic" ? argv[15] : "";
+    const bool mosaic_gain = argc > 16 && std::string(argv[16]) == "gain";
     if ((!warp_file.empty() || !mosaic_file.empty()) && model_name != "homography") {
         std::cerr << "warp and mosaic are for model=homography\n";
         return 1;
@@ -162,7 +164,12 @@ int main(int argc, char** argv) {
             const int cw = (int)(x1 - x0) + 1, ch = (int)(y1 - y0) + 1;
             std::array<f32_t, 9> ident = {1, 0, 0, 0, 1, 0, 0, 0, 1}, hb9;
             std::copy(model.h, model.h + 9, hb9.begin());
-            sift::Image2f pic = matcher.composite({&fa, &fb}, {ident, hb9}, cw, ch, (int)x0, (int)y0);
+            sift::Matcher::Overlap ov;
+            if (mosaic_gain) {
+                ov = matcher.overlap({&fa, &fb}, {ident, hb9}, cw, ch, (int)x0, (int)y0);
+                std::cout << "gains " << ov.gains[0] << ", " << ov.gains[1] << " over " << ov.stats[1] << " common pixels\n";
+            }
+            sift::Image2f pic = matcher.composite({&fa, &fb}, {ident, hb9}, cw, ch, (int)x0, (int)y0, 2, 0.0f, true, nullptr, mosaic_gain ? &ov.gains : nullptr);
             FILE* out = std::fopen(mosaic_file.c_str(), "wb");
             if (!out) throw std::runtime_error("cannot write " + mosaic_file);
             std::fprintf(out, "P5\n%d %d\n255\n", cw, ch);

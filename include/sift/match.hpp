@@ -217,10 +217,13 @@ public:
     // the identity); canvas pixel (x, y) is the lattice point (x + origin_x, y + origin_y).  blend: 0 the first covering
     // frame's value, 1 the mean, 2 feathered by the distance to each frame's border.  Where no frame reaches: `fill`, and 0 in
     // *count (may be null; else the number of covering frames per pixel).  Throws std::invalid_argument for what
-    // sift_hip_composite_homography rejects.
+    // sift_hip_composite_homography rejects.  gains (may be null; else one per frame, as overlap() returns them): frame k's values
+    // are multiplied by (*gains)[k] (sift_hip_composite_homography_gains).
     Image2f composite(const std::vector<Image2f*>& frames, const std::vector<std::array<f32_t, 9>>& models, int out_w, int out_h, int origin_x = 0,
-                      int origin_y = 0, int blend = 2, f32_t fill = 0.0f, bool bilinear = true, std::vector<uint16_t>* count = nullptr) {
+                      int origin_y = 0, int blend = 2, f32_t fill = 0.0f, bool bilinear = true, std::vector<uint16_t>* count = nullptr,
+                      const std::vector<f32_t>* gains = nullptr) {
         if (frames.empty() || frames.size() != models.size()) throw std::invalid_argument("composite: one model per frame, at least one frame");
+        if (gains && gains->size() != frames.size()) throw std::invalid_argument("composite: one gain per frame");
         const size_t w = frames[0]->width(), h = frames[0]->height();
         std::vector<f32_t> stack(frames.size() * w * h);
         for (size_t k = 0; k < frames.size(); ++k) {
@@ -239,11 +242,51 @@ public:
         if (count) count->assign((size_t)out.width() * (size_t)out.height(), 0);
         const int64_t offsets[2] = {0, (int64_t)frames.size()};
         char err[512] = "";
-        const int rc = sift_hip_composite_homography(_ctx, stack.data(), (int)frames.size(), (int)w, (int)h, 1, offsets, nullptr, models[0].data(), &prm,
-                                                     out.data(), count ? count->data() : nullptr, nullptr, err, sizeof(err));
+        const int rc = sift_hip_composite_homography_gains(_ctx, stack.data(), (int)frames.size(), (int)w, (int)h, 1, offsets, nullptr, models[0].data(), &prm,
+                                                           gains ? gains->data() : nullptr, out.data(), count ? count->data() : nullptr, nullptr, err,
+                                                           sizeof(err));
         if (rc == SIFT_HIP_EINVAL) throw std::invalid_argument(err);
         if (rc != SIFT_HIP_OK) throw std::runtime_error(err);
         return out;
+    }
+
+    // The overlap statistics (include/sift_hip.h, "overlap statistics") of `frames` (at most 32, all of one size) placed as for
+    // composite(): stats = 4 x 32 x 32 sums over the canvas pixels that frames i and j both cover - N (pixels), S (q_i), SS
+    // (q_i^2), X (q_i q_j), q the 8-bit intensity round(value * scale) - and one gain per frame (Brown and Lowe's gain
+    // compensation; sigma_n, sigma_g on the 0 .. 255 grid).  solved = false: the solve failed and every gain is 1.
+    struct Overlap {
+        std::vector<int64_t> stats;
+        std::vector<f32_t> gains;
+        bool solved;
+    };
+    Overlap overlap(const std::vector<Image2f*>& frames, const std::vector<std::array<f32_t, 9>>& models, int out_w, int out_h, int origin_x = 0,
+                    int origin_y = 0, f32_t scale = 1.0f, bool bilinear = true, f32_t sigma_n = 10.0f, f32_t sigma_g = 0.1f) {
+        if (frames.empty() || frames.size() != models.size()) throw std::invalid_argument("overlap: one model per frame, at least one frame");
+        const size_t w = frames[0]->width(), h = frames[0]->height();
+        std::vector<f32_t> stack(frames.size() * w * h);
+        for (size_t k = 0; k < frames.size(); ++k) {
+            if (frames[k]->width() != w || frames[k]->height() != h) throw std::invalid_argument("overlap: frames of one size");
+            std::copy(frames[k]->data(), frames[k]->data() + w * h, stack.begin() + k * w * h);
+        }
+        sift_hip_overlap_params prm{};
+        prm.out_w = out_w;
+        prm.out_h = out_h;
+        prm.origin_x = origin_x;
+        prm.origin_y = origin_y;
+        prm.scale = scale;
+        prm.sigma_n = sigma_n;
+        prm.sigma_g = sigma_g;
+        prm.interp = bilinear ? 1 : 0;
+        Overlap r{std::vector<int64_t>(4 * 32 * 32, 0), std::vector<f32_t>(frames.size(), 1.0f), true};
+        const int64_t offsets[2] = {0, (int64_t)frames.size()};
+        uint8_t status = 0;
+        char err[512] = "";
+        const int rc = sift_hip_overlap_stats(_ctx, stack.data(), (int)frames.size(), (int)w, (int)h, 1, offsets, nullptr, models[0].data(), &prm,
+                                              r.stats.data(), r.gains.data(), &status, err, sizeof(err));
+        if (rc == SIFT_HIP_EINVAL) throw std::invalid_argument(err);
+        if (rc != SIFT_HIP_OK) throw std::runtime_error(err);
+        r.solved = status == 0;
+        return r;
     }
 
 private:

@@ -609,6 +609,45 @@ typedef struct sift_hip_composite_params {
 int sift_hip_composite_homography(sift_hip_ctx* ctx, const float* imgs, int n_imgs, int w, int h, int n_canvases, const int64_t* offsets,
                                   const int32_t* src, const float* models, const sift_hip_composite_params* params, float* out,
                                   uint16_t* count, int64_t* tiles, char* err, int errlen);
+/* The same with one gain per job (gains: n_jobs floats, host or device memory): a covering job's value is val = gains[j] * val,
+ * one float rounding, wherever the blend takes its value; everything else, and every check, as above.  gains NULL: the call
+ * above, bit for bit.  The gains of frames exposed differently come from the overlap statistics below. */
+int sift_hip_composite_homography_gains(sift_hip_ctx* ctx, const float* imgs, int n_imgs, int w, int h, int n_canvases,
+                                        const int64_t* offsets, const int32_t* src, const float* models,
+                                        const sift_hip_composite_params* params, const float* gains, float* out, uint16_t* count,
+                                        int64_t* tiles, char* err, int errlen);
+
+/* ---- overlap statistics and gain compensation (an extension) ------------------------------------------------
+ * The photometric statistics of every pair of a canvas's jobs where both cover the canvas, without writing a canvas: the input
+ * of gain compensation (Brown and Lowe 2007, section 6) and of the zero-mean normalised cross-correlation of a registered pair.
+ * Canvases, jobs, models, src and the lattice are the compositor's; a canvas has at most 32 jobs.  sift_amd/csrc/overlap_math.h
+ * defines every bit; the kernels and a plain host loop (hostmath_overlap_stats) compile it.  For canvas pixel (x, y) and job i:
+ * c_i = the warp's coverage test, q_i = the warp's value there quantised as the 8-bit descriptors are, t = fmaf(val, scale,
+ * 0.5f), q = t >= 255 ? 255 : (t >= 0 ? (int)t : 0) (a NaN: 0).  stats[c][4][32][32] holds, for all ordered (i, j), i == j
+ * included, the sums over all canvas pixels where c_i and c_j both hold of
+ *   plane 0  N[i][j]: 1      plane 1  S[i][j]: q_i      plane 2  SS[i][j]: q_i q_i      plane 3  X[i][j]: q_i q_j
+ * and zeros in rows and columns >= n.  The sums are integers (formed on the i8 matrix instruction): exact, the same for every
+ * `path` and launch.  gains (may be NULL) receives one float per job, the solution in double of the normal equations of
+ *   sum_ij N_ij ((g_i I_ij - g_j I_ji)^2 / sigma_n^2 + (1 - g_i)^2 / sigma_g^2),  I_ij = S_ij / N_ij,
+ * as OpenCV's gain compensator forms them, by Gaussian elimination with partial pivoting, every update one fma; a job that
+ * covers nothing has gain 1.  status (may be NULL; written when gains is given) is 1 for a canvas whose solve failed (a zero
+ * pivot, a gain not finite or <= 0): all its gains are then 1.0f. */
+typedef struct sift_hip_overlap_params {
+    int32_t out_w, out_h;        /* > 0 */
+    int32_t origin_x, origin_y;  /* as for the compositor */
+    float scale;                 /* q = round(val * scale): 1 for frames of 0 .. 255, 255 for frames in [0, 1]; finite, > 0 */
+    float sigma_n, sigma_g;      /* on the 0 .. 255 grid; OpenCV's defaults are 10 and 0.1; finite, > 0 when gains is given */
+    uint8_t interp;              /* 0 nearest, 1 bilinear; above: EINVAL */
+    uint8_t path;                /* 0: a region's 16 chunks share one flush; 1: every chunk is flushed by itself (same bits; measurement and tests) */
+    uint8_t reserved[2];         /* zero */
+} sift_hip_overlap_params;       /* 32 bytes */
+/* imgs, models, stats (n_canvases x 4 x 32 x 32 int64), gains (n_jobs) and status (n_canvases) may each be host or device
+ * memory; offsets and src are host arrays.  Scratch memory, stream and "not while a batch is in flight" as for the warp.
+ * SIFT_HIP_EINVAL for the compositor's conditions, more than 32 jobs in one canvas, a scale (or, with gains, a sigma) that is
+ * not finite or <= 0, a bad interp or path, or non-zero reserved bytes. */
+int sift_hip_overlap_stats(sift_hip_ctx* ctx, const float* imgs, int n_imgs, int w, int h, int n_canvases, const int64_t* offsets,
+                           const int32_t* src, const float* models, const sift_hip_overlap_params* params, int64_t* stats,
+                           float* gains, uint8_t* status, char* err, int errlen);
 
 /* ---- inspection of the last batch (parity tests) ------------------------------------------------ */
 /* kind: 0 gaussian (levels 0..D), 1 dog (0..D-1), 2 magnitude, 3 orientation (initial gradient

@@ -44,6 +44,7 @@ SYMBOLS = [
     "sift_hip_knn2_guided_u8", "sift_hip_match_guided_u8", "sift_hip_result_match_guided_u8",
     "sift_hip_result_localize", "sift_hip_localize_points",
     "sift_hip_warp_homography", "sift_hip_composite_homography",
+    "sift_hip_composite_homography_gains", "sift_hip_overlap_stats",
 ]
 
 
@@ -80,6 +81,14 @@ class CompositeParams(C.Structure):
 
 
 COMPOSITE_BLEND = {"first": 0, "mean": 1, "feather": 2}
+
+
+class OverlapParams(C.Structure):
+    _fields_ = [("out_w", C.c_int32), ("out_h", C.c_int32), ("origin_x", C.c_int32), ("origin_y", C.c_int32), ("scale", C.c_float),
+                ("sigma_n", C.c_float), ("sigma_g", C.c_float), ("interp", C.c_uint8), ("path", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+OVERLAP_MAX_JOBS = 32
 
 
 class RansacParams(C.Structure):
@@ -258,5 +267,9 @@ def load():
     L.sift_hip_warp_homography.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, C.POINTER(WarpParams), vp, vp, vp, cs, ci]
     # imgs, models, out and count: host or device memory; offsets, src and tiles: host arrays (src, tiles: or None)
     L.sift_hip_composite_homography.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, C.POINTER(CompositeParams), vp, vp, vp, cs, ci]
+    # the compositor's arguments with gains (host or device memory) before out
+    L.sift_hip_composite_homography_gains.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, C.POINTER(CompositeParams), vp, vp, vp, vp, cs, ci]
+    # imgs, models, stats, gains and status: host or device memory; offsets and src: host arrays (src: or None)
+    L.sift_hip_overlap_stats.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, C.POINTER(OverlapParams), vp, vp, vp, cs, ci]
     _lib = L
     return L

@@ -6,7 +6,7 @@ overlay :59-76) on top of the GPU path — SURVEY.md §8(f) rows 1-3.
     python -m sift_amd.cli -i a.pgm --match b.pgm --u8 [--verify ...]                (8-bit descriptors, integer distances)
     python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--iterations 2048] [--threshold 3] [--seed 0] [--refine 0] [--model homography|fundamental] [--refit N] [--localize]   (... and inliers.txt)
     python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--refine N] --warp out.png   (... and b registered onto a: the homography warp)
-    python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--refine N] --mosaic out.png [--blend first|mean|feather]   (... and both frames on the canvas that holds them: the compositor)
+    python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--refine N] --mosaic out.png [--blend first|mean|feather] [--gain]   (... and both frames on the canvas that holds them: the compositor)
     python -m sift_amd.cli -i a.pgm --match b.pgm --verify --guided [--guided-ratio R]   (... and guided.txt: the matches again, under the verified model)
 
 Image ingest follows Vigra's scalar import: band 0 of multi-band files, values unscaled.  PGM,
@@ -162,6 +162,8 @@ def main(argv=None) -> int:
                     help="with --verify (a homography; both images of one size): the image and IMG2 blended on the canvas that holds both "
                          "frames, written as PNG like --warp (black where neither reaches)")
     ap.add_argument("--blend", choices=["first", "mean", "feather"], default="feather", help="how --mosaic blends where the frames overlap")
+    ap.add_argument("--gain", action="store_true",
+                    help="with --mosaic: solve one gain per frame from the frames' overlap first (gain compensation) and blend the gained frames")
     ap.add_argument("--u8", action="store_true",
                     help="with --match: quantise the descriptors to 8 bits on the GPU and match by the integer distance (the distances "
                          "in matches.txt are integers)")
@@ -178,6 +180,8 @@ def main(argv=None) -> int:
         ap.error("--warp needs --verify with --model homography")
     if args.mosaic and not (args.verify and args.model == "homography"):
         ap.error("--mosaic needs --verify with --model homography")
+    if args.gain and not args.mosaic:
+        ap.error("--gain needs --mosaic")
     if args.u8 and args.guided:
         ap.error("--u8 cannot be combined with --guided: guided matching takes float descriptors only")
     if args.guided_u8 and not args.verify:
@@ -253,7 +257,11 @@ def main(argv=None) -> int:
                     frames = np.stack([np.asarray(img, np.float32), read_image(args.match).astype(np.float32)])
                     (ox, oy), shape = sift.mosaic_canvas(np.asarray(model["h"], np.float32)[None] if model["iteration"] >= 0 else [], *frames.shape[:0:-1])
                     jobs = np.array([[1, 0, 0, 0, 1, 0, 0, 0, 1], model["h"]], np.float32)[:2 if model["iteration"] >= 0 else 1]
-                    pic, cover = sift.ctx.composite_homography(frames, jobs, out_shape=shape, origin=(ox, oy), blend=args.blend, count=True)
+                    gains = None
+                    if args.gain:
+                        stats, gains, _ = sift.ctx.overlap_stats(frames, jobs, out_shape=shape, origin=(ox, oy), gains=True)
+                        print(f"gains {' '.join(f'{g:.4f}' for g in gains)}; ZNCC over the overlap {sift.ctx.overlap_zncc(stats[0], len(jobs))[0, -1]:.4f}")
+                    pic, cover = sift.ctx.composite_homography(frames, jobs, out_shape=shape, origin=(ox, oy), blend=args.blend, count=True, gains=gains)
                     grey = np.clip(np.rint(pic[0]), 0, 255).astype(np.uint8)
                     _err_call(_lib.load().sift_hip_png_write_bgr8, args.mosaic.encode(), np.ascontiguousarray(np.repeat(grey[:, :, None], 3, axis=2)).reshape(-1), shape[1], shape[0])
                     print(f"{args.img} + {args.match} -> {args.mosaic} ({shape[1]} x {shape[0]}, origin {ox}, {oy}; {int((cover == 2).sum())} pixels under both)")

@@ -1,4 +1,4 @@
-// Host side of the compositor (include/sift_hip.h: sift_hip_composite_homography): checks, staging of caller memory and the
+// Host side of the compositor (include/sift_hip.h: sift_hip_composite_homography and its _gains form): checks, staging of caller memory and the
 // scratch memory, which the first call of a context allocates and the context keeps - outside the batch arena, like the warp's.
 // The kernel: kernels_composite.hip; the definition: composite_math.h.
 #include <climits>
@@ -12,14 +12,14 @@
 namespace sift_hip {
 
 struct CompositeState {
-    ScratchBuf d_imgs, d_models, d_src, d_offsets;   // what arrives in host memory
+    ScratchBuf d_imgs, d_models, d_src, d_offsets, d_gains;   // what arrives in host memory
     ScratchBuf d_out, d_count;                       // results on their way to host memory
     ScratchBuf d_tiles;                              // the three visit counters
 };
 
 void composite_state_free(CompositeState* st) {
     if (!st) return;
-    for (ScratchBuf* b : {&st->d_imgs, &st->d_models, &st->d_src, &st->d_offsets, &st->d_out, &st->d_count, &st->d_tiles}) b->release();
+    for (ScratchBuf* b : {&st->d_imgs, &st->d_models, &st->d_src, &st->d_offsets, &st->d_gains, &st->d_out, &st->d_count, &st->d_tiles}) b->release();
     delete st;
 }
 
@@ -36,6 +36,7 @@ struct Job {
     float* out;
     uint16_t* count;
     int64_t* tiles;
+    const float* gains;   // one per job, host or device memory; null: none
     char* err;
     int errlen;
 };
@@ -109,6 +110,13 @@ int run(void* arg) {
     st.d_offsets.ensure(off_bytes);
     match_upload(j.c, st.d_offsets.p, j.offsets, off_bytes);
     match_wait(j.c);
+    const float* d_gains = n_jobs > 0 ? j.gains : nullptr;
+    if (d_gains && !match_ptr_on_device(j.gains)) {
+        st.d_gains.ensure((size_t)n_jobs * sizeof(float));
+        match_upload(j.c, st.d_gains.p, j.gains, (size_t)n_jobs * sizeof(float));
+        match_wait(j.c);
+        d_gains = st.d_gains.as<float>();
+    }
 
     // ---- results: written in place when the caller's array is device memory ----
     const bool out_direct = match_ptr_on_device(j.out), count_direct = j.count && match_ptr_on_device(j.count);
@@ -125,7 +133,7 @@ int run(void* arg) {
 
     const CompositeArgs a{p->out_w, p->out_h, p->origin_x, p->origin_y, p->fill, (int)p->interp, (int)p->blend, (int)p->path,
                           (j.w % 4 == 0 && (reinterpret_cast<uintptr_t>(d_imgs) & 15u) == 0) ? 1 : 0};
-    launch_composite(v.stream, d_imgs, j.w, j.h, d_src, d_models, st.d_offsets.as<long long>(), j.n_canvases, a, d_out, d_count, d_tiles);
+    launch_composite(v.stream, d_imgs, j.w, j.h, d_src, d_models, st.d_offsets.as<long long>(), j.n_canvases, a, d_out, d_count, d_tiles, d_gains);
     SIFT_HIP_CHECK(hipGetLastError());
 
     if (!out_direct) match_download(j.c, j.out, d_out, px * sizeof(float));
@@ -144,6 +152,14 @@ extern "C" int sift_hip_composite_homography(sift_hip_ctx* c, const float* imgs,
                                              const int32_t* src, const float* models, const sift_hip_composite_params* params, float* out, uint16_t* count,
                                              int64_t* tiles, char* err, int errlen) {
     if (!c) { match_set_err(err, errlen, "sift_hip_composite_homography: no context (the compositor runs on the GPU only)"); return SIFT_HIP_EINVAL; }
-    Job j{c, imgs, n_imgs, w, h, n_canvases, offsets, src, models, params, out, count, tiles, err, errlen};
+    Job j{c, imgs, n_imgs, w, h, n_canvases, offsets, src, models, params, out, count, tiles, nullptr, err, errlen};
+    return match_guarded(err, errlen, run, &j);
+}
+
+extern "C" int sift_hip_composite_homography_gains(sift_hip_ctx* c, const float* imgs, int n_imgs, int w, int h, int n_canvases, const int64_t* offsets,
+                                                   const int32_t* src, const float* models, const sift_hip_composite_params* params, const float* gains,
+                                                   float* out, uint16_t* count, int64_t* tiles, char* err, int errlen) {
+    if (!c) { match_set_err(err, errlen, "sift_hip_composite_homography_gains: no context (the compositor runs on the GPU only)"); return SIFT_HIP_EINVAL; }
+    Job j{c, imgs, n_imgs, w, h, n_canvases, offsets, src, models, params, out, count, tiles, gains, err, errlen};
     return match_guarded(err, errlen, run, &j);
 }

@@ -27,9 +27,9 @@ struct CompositeArgs {
 
 // every canvas in one launch: canvas c accumulates jobs d_offsets[c] .. d_offsets[c + 1] - 1 (job j reads image d_src[j]; d_src
 // null: image j) into d_out[c] and, unless null, d_count[c]; d_tiles (three counters, zeroed by the caller: (tile, job) visits
-// staged, direct, skipped) may be null
+// staged, direct, skipped) may be null; d_gains (one float per job) may be null: no gains
 void launch_composite(hipStream_t s, const float* d_imgs, int w, int h, const int* d_src, const float* d_models, const long long* d_offsets, int n_canvases,
-                      const CompositeArgs& a, float* d_out, uint16_t* d_count, unsigned long long* d_tiles);
+                      const CompositeArgs& a, float* d_out, uint16_t* d_count, unsigned long long* d_tiles, const float* d_gains);
 void tu_touch_composite(hipStream_t s);
 
 // ---- the context as composite.cpp sees it (context.cpp); uploads, downloads and errors go through the match_* accessors ----

@@ -14,6 +14,8 @@
 //                        source frame's border plus one, >= 1 for a covered pixel, the same u, v for both interp values -,
 //                        acc = fmaf(wgt, val, acc), wsum = wsum + wgt
 //   result     cnt == 0: fill; first: the kept val; mean: acc / (float)cnt; feather: acc / wsum (correctly rounded quotients)
+// With gains (sift_hip_composite_homography_gains; the overlap statistics solve them, overlap_math.h) a covering job's value is
+// val = gains[j] * val, one float rounding, wherever its value is wanted at all; without, nothing changes.
 // The value depends on the inputs alone: not on tiles, paths, culling or the launch.
 #pragma once
 #include <stdint.h>
@@ -58,7 +60,7 @@ SIFT_HD float composite_result(const CompositeAcc& a, float fill, int blend) {
 
 // one canvas pixel from the definition: jobs j0 .. j1 - 1 in order
 SIFT_HD float composite_pixel(const float* imgs, int w, int hgt, const int32_t* src, const float* models, long long j0, long long j1, int x, int y, int origin_x,
-                              int origin_y, float fill, int interp, int blend, uint16_t& count) {
+                              int origin_y, float fill, int interp, int blend, uint16_t& count, const float* gains = nullptr) {
     CompositeAcc a = {0.0f, 0.0f, 0u};
     const float qx = (float)(x + origin_x), qy = (float)(y + origin_y);
     for (long long j = j0; j < j1; ++j) {
@@ -70,6 +72,7 @@ SIFT_HD float composite_pixel(const float* imgs, int w, int hgt, const int32_t* 
             const float* s = imgs + (size_t)(src ? src[j] : j) * (size_t)w * (size_t)hgt;
             const WarpTaps t = warp_taps(u, v, w, hgt, interp);
             val = warp_value([&](int px, int py) { return s[(size_t)py * (size_t)w + (size_t)px]; }, t, interp);
+            if (gains) val = gains[j] * val;
         }
         composite_add(a, val, blend == 2 ? composite_weight(u, v, w, hgt) : 0.0f, blend);
     }

@@ -15,6 +15,7 @@
 #include "localize_math.h"
 #include "warp_math.h"
 #include "composite_math.h"
+#include "overlap_math.h"
 #include "../../include/sift_hip.h"   // sift_hip_homography, sift_hip_fundamental
 
 extern "C" {
@@ -678,5 +679,40 @@ void hostmath_composite_homography(const float* imgs, int w, int h, int n_canvas
                 out[o] = composite_pixel(imgs, w, h, src, models, offsets[c], offsets[c + 1], x, y, p->origin_x, p->origin_y, p->fill, p->interp, p->blend, cnt);
                 if (count) count[o] = cnt;
             }
+}
+}
+
+// ---- compositor with gains, overlap statistics and gains (composite_math.h, overlap_math.h): the plain loops ------------
+extern "C" {
+void hostmath_composite_homography_gains(const float* imgs, int w, int h, int n_canvases, const int64_t* offsets, const int32_t* src, const float* models,
+                                         const sift_hip_composite_params* p, const float* gains, float* out, uint16_t* count) {
+    using namespace sift_hip;
+    const size_t px = (size_t)p->out_w * (size_t)p->out_h;
+    for (int c = 0; c < n_canvases; ++c)
+        for (int y = 0; y < p->out_h; ++y)
+            for (int x = 0; x < p->out_w; ++x) {
+                uint16_t cnt;
+                const size_t o = (size_t)c * px + (size_t)y * (size_t)p->out_w + (size_t)x;
+                out[o] = composite_pixel(imgs, w, h, src, models, offsets[c], offsets[c + 1], x, y, p->origin_x, p->origin_y, p->fill, p->interp, p->blend, cnt, gains);
+                if (count) count[o] = cnt;
+            }
+}
+
+// canvas c: the statistics of jobs offsets[c] .. offsets[c + 1] - 1 (at most 32) -> stats[c] (4 x 32 x 32) and, unless null,
+// gains[offsets[c] ..] and status[c]
+void hostmath_overlap_stats(const float* imgs, int w, int h, int n_canvases, const int64_t* offsets, const int32_t* src, const float* models,
+                            const sift_hip_overlap_params* p, int64_t* stats, float* gains, uint8_t* status) {
+    using namespace sift_hip;
+    for (int c = 0; c < n_canvases; ++c) {
+        int64_t* st = stats + (size_t)c * kOverlapStats;
+        const int n = (int)(offsets[c + 1] - offsets[c]);
+        for (int k = 0; k < kOverlapStats; ++k) st[k] = 0;
+        for (int y = 0; y < p->out_h; ++y)
+            for (int x = 0; x < p->out_w; ++x) overlap_pixel(imgs, w, h, src, models, offsets[c], n, x, y, p->origin_x, p->origin_y, p->scale, p->interp, st);
+        if (gains) {
+            const int bad = gain_solve(st, n, p->sigma_n, p->sigma_g, gains + offsets[c]);
+            if (status) status[c] = (uint8_t)bad;
+        }
+    }
 }
 }

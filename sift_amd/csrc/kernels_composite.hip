@@ -48,9 +48,12 @@ struct Visit {
 
 }  // namespace
 
+// kGains: a covering job's value is multiplied by gains[job] (composite_math.h); the call without gains runs the <false> instantiation
+template <bool kGains>
 __global__ __launch_bounds__(kCompLanes) void composite_kernel(const float* __restrict__ imgs, int w, int h, const int* __restrict__ src,
                                                                const float* __restrict__ models, const long long* __restrict__ offsets, CompositeArgs a,
-                                                               float* __restrict__ out, uint16_t* __restrict__ count, unsigned long long* __restrict__ tiles) {
+                                                               float* __restrict__ out, uint16_t* __restrict__ count, unsigned long long* __restrict__ tiles,
+                                                               const float* __restrict__ gains) {
     __shared__ float box[2][kCompBoxFloats];
     __shared__ unsigned flags[2][kCompWaves];
     const int tid = threadIdx.x, wave = tid >> 6, canvas = blockIdx.z;
@@ -154,6 +157,7 @@ __global__ __launch_bounds__(kCompLanes) void composite_kernel(const float* __re
                     const bool inbox = (t.x0 >= old.bx0) & (t.x1 < old.bx0 + old.bw) & (t.y0 >= old.by0) & (t.y1 < old.by0 + old.bh);
                     if (inbox) val = warp_value([&](int px, int py) { return b[(py - old.by0) * old.pitch + (px - old.bx0)]; }, t, a.interp);
                     else val = warp_value([&](int px, int py) { return s[(size_t)py * (size_t)w + (size_t)px]; }, t, a.interp);
+                    if constexpr (kGains) val = gains[p - 2] * val;
                 }
                 composite_add(acc[r], val, a.blend == 2 ? composite_weight(old.u[r], old.v[r], w, h) : 0.0f, a.blend);
             }
@@ -181,10 +185,11 @@ __global__ __launch_bounds__(kCompLanes) void composite_kernel(const float* __re
 __global__ void tu_probe_composite_kernel() {}
 
 void launch_composite(hipStream_t s, const float* d_imgs, int w, int h, const int* d_src, const float* d_models, const long long* d_offsets, int n_canvases,
-                      const CompositeArgs& a, float* d_out, uint16_t* d_count, unsigned long long* d_tiles) {
+                      const CompositeArgs& a, float* d_out, uint16_t* d_count, unsigned long long* d_tiles, const float* d_gains) {
     if (n_canvases <= 0) return;
     const dim3 grid((unsigned)((a.out_w + kCompTileW - 1) / kCompTileW), (unsigned)((a.out_h + kCompTileH - 1) / kCompTileH), (unsigned)n_canvases);
-    hipLaunchKernelGGL(composite_kernel, grid, dim3(kCompLanes), 0, s, d_imgs, w, h, d_src, d_models, d_offsets, a, d_out, d_count, d_tiles);
+    if (d_gains) hipLaunchKernelGGL(composite_kernel<true>, grid, dim3(kCompLanes), 0, s, d_imgs, w, h, d_src, d_models, d_offsets, a, d_out, d_count, d_tiles, d_gains);
+    else hipLaunchKernelGGL(composite_kernel<false>, grid, dim3(kCompLanes), 0, s, d_imgs, w, h, d_src, d_models, d_offsets, a, d_out, d_count, d_tiles, d_gains);
 }
 
 void tu_touch_composite(hipStream_t s) { hipLaunchKernelGGL(tu_probe_composite_kernel, dim3(1), dim3(1), 0, s); }

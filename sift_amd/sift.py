@@ -915,14 +915,15 @@ class Context:
 
     # ---- compositor (include/sift_hip.h, "compositor") ---------------------------------------------------------
     def composite_homography(self, imgs, models, offsets=None, src=None, out_shape=None, origin=(0, 0), fill=0.0, interp="bilinear", blend="feather",
-                             path=0, out=None, count=False, want_tiles=False, shape=None):
+                             path=0, out=None, count=False, want_tiles=False, shape=None, gains=None):
         """sift_hip_composite_homography: canvas c accumulates jobs offsets[c] .. offsets[c + 1] - 1 in order, job j being image
         src[j] (None: image j) under models[j] as in warp_homography -> (out[, count][, tiles]): out [n_canvases, out_h, out_w]
         float32, one picture per canvas; count uint16, the jobs that cover each pixel (0: `fill`); tiles = (staged, direct,
         skipped) (tile, job) visits with `want_tiles`.  `offsets` None: one canvas of all jobs.  `blend`: "first" (the first
         covering job's value), "mean" or "feather" (weights: distance to the source frame's border plus one).  `imgs`, `models`,
         `out_shape`, `origin`, `interp`, `path`, `shape` as in warp_homography; `out`, and `count` when it is not a bool: where
-        a result goes (returned as given)."""
+        a result goes (returned as given).  `gains` (sift_hip_composite_homography_gains): one float per job, numbers, a tensor
+        or an address - a covering job's value is multiplied by its gain (overlap_stats solves them); None: no gains."""
         if isinstance(imgs, np.ndarray):
             imgs = np.ascontiguousarray(imgs, np.float32)
             imgs = imgs[None] if imgs.ndim == 2 else imgs
@@ -956,12 +957,77 @@ class Context:
         cnt = (np.zeros(size, np.uint16) if count else None) if isinstance(count, bool) else count
         tiles = np.zeros(3, np.int64) if want_tiles else None
         err = C.create_string_buffer(512)
-        rc = self._L.sift_hip_composite_homography(self._h, self._addr(imgs), int(shape[0]), int(shape[2]), int(shape[1]), offsets.size - 1, self._addr(offsets),
-                                                   self._addr(src), self._addr(models), C.byref(prm), self._addr(res), self._addr(cnt), self._addr(tiles), err, 512)
+        head = (self._h, self._addr(imgs), int(shape[0]), int(shape[2]), int(shape[1]), offsets.size - 1, self._addr(offsets), self._addr(src),
+                self._addr(models), C.byref(prm))
+        if gains is None:
+            rc = self._L.sift_hip_composite_homography(*head, self._addr(res), self._addr(cnt), self._addr(tiles), err, 512)
+        else:
+            if isinstance(gains, (np.ndarray, list, tuple)):
+                gains = np.ascontiguousarray(gains, np.float32).reshape(-1)
+                if gains.size != n_jobs:
+                    raise ValueError("composite_homography: one gain per model")
+            rc = self._L.sift_hip_composite_homography_gains(*head, self._addr(gains), self._addr(res), self._addr(cnt), self._addr(tiles), err, 512)
         if rc:
             _raise(rc, err)
         got = (res,) + ((cnt,) if cnt is not None else ()) + ((tuple(int(t) for t in tiles),) if want_tiles else ())
         return got[0] if len(got) == 1 else got
+
+    # ---- overlap statistics and gains (include/sift_hip.h, "overlap statistics") -------------------------------
+    def overlap_stats(self, imgs, models, offsets=None, src=None, out_shape=None, origin=(0, 0), scale=1.0, interp="bilinear", gains=False,
+                      sigma_n=10.0, sigma_g=0.1, path=0, shape=None, stats=None):
+        """sift_hip_overlap_stats: for canvas c and its jobs offsets[c] .. offsets[c + 1] - 1 (at most 32; job j is image src[j]
+        under models[j], as in composite_homography) the sums, over the canvas pixels that jobs i and j both cover, of 1, q_i,
+        q_i^2 and q_i q_j with q the 8-bit intensity round(value * scale) -> stats int64 [n_canvases, 4, 32, 32] (planes N, S,
+        SS, X; rows and columns past a canvas's jobs are zero); with `gains` (stats, gains, status): one float32 gain per job,
+        Brown and Lowe's gain compensation with `sigma_n`, `sigma_g` on the 0 .. 255 grid, and one byte per canvas, 1 where
+        the solve failed and the canvas's gains are all 1.  `scale`: 1 for frames of 0 .. 255, 255 for frames in [0, 1].
+        `path` 1: every chunk of pixels is flushed by itself (the same bits).  `stats`, and `gains` when it is not a bool:
+        where a result goes (returned as given).  The other arguments as in composite_homography."""
+        if isinstance(imgs, np.ndarray):
+            imgs = np.ascontiguousarray(imgs, np.float32)
+            imgs = imgs[None] if imgs.ndim == 2 else imgs
+            shape = imgs.shape
+        elif shape is None:
+            shape = tuple(imgs.shape)   # a tensor
+        if len(shape) != 3:
+            raise ValueError("overlap_stats: imgs is [n, h, w]")
+        if interp not in _lib.WARP_INTERP:
+            raise ValueError('overlap_stats: interp must be "nearest" or "bilinear"')
+        if isinstance(models, np.ndarray) and models.dtype.names:
+            models = models["h"]
+        if isinstance(models, (np.ndarray, list, tuple)):
+            models = np.ascontiguousarray(models, np.float32).reshape(-1, 9)
+            n_jobs = models.shape[0]
+        else:
+            n_jobs = len(src) if src is not None else int(shape[0])
+        if src is not None:
+            src = np.ascontiguousarray(src, np.int32).reshape(-1)
+            if src.size != n_jobs:
+                raise ValueError("overlap_stats: one src index per model")
+        offsets = np.array([0, n_jobs], np.int64) if offsets is None else np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        if offsets.size < 1 or offsets[-1] != n_jobs:
+            raise ValueError("overlap_stats: offsets has one entry per canvas and one more, the last being the number of models")
+        oh, ow = (int(shape[1]), int(shape[2])) if out_shape is None else (int(out_shape[0]), int(out_shape[1]))
+        prm = _lib.OverlapParams(ow, oh, int(origin[0]), int(origin[1]), float(scale), float(sigma_n), float(sigma_g), _lib.WARP_INTERP[interp], int(path) & 0xff)
+        res = np.zeros((offsets.size - 1, 4, _lib.OVERLAP_MAX_JOBS, _lib.OVERLAP_MAX_JOBS), np.int64) if stats is None else stats
+        g = (np.ones(n_jobs, np.float32) if gains else None) if isinstance(gains, bool) else gains
+        status = np.zeros(offsets.size - 1, np.uint8) if g is not None else None
+        err = C.create_string_buffer(512)
+        rc = self._L.sift_hip_overlap_stats(self._h, self._addr(imgs), int(shape[0]), int(shape[2]), int(shape[1]), offsets.size - 1, self._addr(offsets),
+                                            self._addr(src), self._addr(models), C.byref(prm), self._addr(res), self._addr(g), self._addr(status), err, 512)
+        if rc:
+            _raise(rc, err)
+        return res if g is None else (res, g, status)
+
+    @staticmethod
+    def overlap_zncc(stats, n):
+        """The zero-mean normalised cross-correlation of every pair of the first `n` jobs of ONE canvas's `stats` [4, 32, 32]
+        over the pair's overlap, host numpy in float64: (N X - S_ij S_ji) / sqrt((N SS_ij - S_ij^2) (N SS_ji - S_ji^2)), NaN
+        where a factor is <= 0 (no overlap, or a constant frame there)."""
+        N, S, SS, X = (np.asarray(stats)[k, :n, :n].astype(np.float64) for k in range(4))
+        vi, vj = N * SS - S * S, N * SS.T - S.T * S.T
+        with np.errstate(all="ignore"):
+            return np.where((vi > 0) & (vj > 0), (N * X - S * S.T) / np.sqrt(vi * vj), np.nan)
 
 
 class Group:
@@ -1216,7 +1282,7 @@ class Sift:
 
     def mosaic(self, imgs, ref: int = 0, pairs=None, blend: str = "feather", ratio: float = 0.8, cross_check: bool = False, iterations: int = 2048,
                threshold: float = 3.0, seed: int = 0, refine: int = 0, quantized: bool = False, fill: float = 0.0, interp: str = "bilinear",
-               chain: bool = False, canvas=None):
+               chain: bool = False, canvas=None, gain: bool = False, scale: float = 1.0):
         """A mosaic or a stack (an extension): calculate() on every frame of `imgs` [n, h, w], verify() on every pair (query,
         train) and Context.composite_homography of the placed frames on one canvas in frame `ref`'s coordinates -> (models,
         canvas, count, origin): one homography record per pair, the picture [out_h, out_w], the number of frames that cover each
@@ -1226,7 +1292,9 @@ class Sift:
         once to float.  Job 0 is frame `ref` under the identity, then the train frames in the pairs' order; a frame without a
         model (or behind one in its chain) is left out, and a frame is placed once, by its first pair.  `canvas` None: the box, computed in float64, of every placed frame's
         corners through its inverse model, each side clipped to 4 x the frame's larger side around frame `ref`; else (origin,
-        shape) = ((x, y), (out_h, out_w)).  Bit for bit the composition of those calls."""
+        shape) = ((x, y), (out_h, out_w)).  Bit for bit the composition of those calls.  `gain`: Context.overlap_stats(gains=True, scale=`scale`)
+        on the same canvas first, the gains given to the compositor -> (models, canvas, count, origin, gains, zncc): one gain
+        per placed frame in job order and Context.overlap_zncc of the placed frames (at most 32)."""
         imgs = np.asarray(imgs)
         if imgs.ndim != 3:
             raise ValueError("mosaic: imgs is [n, h, w]")
@@ -1252,6 +1320,10 @@ class Sift:
             origin, shape = self.mosaic_canvas(job_models[1:], w, h)
         else:
             origin, shape = (int(canvas[0][0]), int(canvas[0][1])), (int(canvas[1][0]), int(canvas[1][1]))
+        if gain:
+            stats, gains, _ = self.ctx.overlap_stats(imgs.astype(np.float32), job_models, None, src, shape, origin, scale, interp, gains=True)
+            out, count = self.ctx.composite_homography(imgs.astype(np.float32), job_models, None, src, shape, origin, fill, interp, blend, count=True, gains=gains)
+            return models, out[0], count[0], origin, gains, self.ctx.overlap_zncc(stats[0], len(src))
         out, count = self.ctx.composite_homography(imgs.astype(np.float32), job_models, None, src, shape, origin, fill, interp, blend, count=True)
         return models, out[0], count[0], origin
 
