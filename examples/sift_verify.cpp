@@ -3,10 +3,11 @@
 // or, with model=fundamental, sift::Matcher::verify_fundamental(): a seven-point fundamental matrix, the model for two views of a
 // general scene.  inliers.txt holds the lines of matches.txt that agree with the model.
 //   g++ -std=c++17 -pthread -Iinclude examples/sift_verify.cpp -Lsift_amd/lib -lsift_hip -Wl,-rpath,$PWD/sift_amd/lib -o sift_verify
-//   ./sift_verify a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [refine=0] [model=homography|fundamental] [refit=-1] [localize=0] [warp|mosaic out.pgm [gain]]
+//   ./sift_verify a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [refine=0] [model=homography|fundamental] [refit=-1] [localize=0] [warp|mosaic out.pgm [gain] [twoband]]
 //   ... warp out.pgm (with model=homography): b registered onto a under the verified model (sift::Matcher::warp), as an 8-bit PGM
 //   ... mosaic out.pgm (likewise; a and b of one size): both frames feathered on the canvas that holds them (sift::Matcher::composite)
 //   ... mosaic out.pgm gain: the frames' gains are solved from their overlap first (sift::Matcher::overlap) and applied
+//   ... mosaic out.pgm twoband: blended in two frequency bands of sigma 5 instead (sift::Matcher::composite_twoband), also after gain
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -65,7 +66,11 @@ int main(int argc, char** argv) {
     const std::string warp_file = argc > 15 && std::string(argv[14]) == "warp" ? argv[15] : "";
     // "mosaic out.pgm": a under the identity and b under the verified homography on one canvas
     const std::string mosaic_file = argc > 15 && std::string(argv[14]) == "mosaic" ? argv[15] : "";
-    const bool mosaic_gain = argc > 16 && std::string(argv[16]) == "gain";
+    bool mosaic_gain = false, mosaic_twoband = false;   // "gain" and "twoband" after the file, in either order
+    for (int k = 16; k < argc && k < 18; ++k) {
+        mosaic_gain |= std::string(argv[k]) == "gain";
+        mosaic_twoband |= std::string(argv[k]) == "twoband";
+    }
     if ((!warp_file.empty() || !mosaic_file.empty()) && model_name != "homography") {
         std::cerr << "warp and mosaic are for model=homography\n";
         return 1;
@@ -169,7 +174,9 @@ int main(int argc, char** argv) {
                 ov = matcher.overlap({&fa, &fb}, {ident, hb9}, cw, ch, (int)x0, (int)y0);
                 std::cout << "gains " << ov.gains[0] << ", " << ov.gains[1] << " over " << ov.stats[1] << " common pixels\n";
             }
-            sift::Image2f pic = matcher.composite({&fa, &fb}, {ident, hb9}, cw, ch, (int)x0, (int)y0, 2, 0.0f, true, nullptr, mosaic_gain ? &ov.gains : nullptr);
+            const std::vector<f32_t>* gains = mosaic_gain ? &ov.gains : nullptr;
+            sift::Image2f pic = mosaic_twoband ? matcher.composite_twoband({&fa, &fb}, {ident, hb9}, cw, ch, (int)x0, (int)y0, 5.0f, 0.0f, true, nullptr, gains)
+                                               : matcher.composite({&fa, &fb}, {ident, hb9}, cw, ch, (int)x0, (int)y0, 2, 0.0f, true, nullptr, gains);
             FILE* out = std::fopen(mosaic_file.c_str(), "wb");
             if (!out) throw std::runtime_error("cannot write " + mosaic_file);
             std::fprintf(out, "P5\n%d %d\n255\n", cw, ch);

@@ -250,6 +250,46 @@ public:
         return out;
     }
 
+    // The two-band compositor (include/sift_hip.h, "two-band compositor"): composite()'s frames, models, canvas, fill, count and
+    // gains, blended in two frequency bands - each frame's low band (a Gaussian blur of `sigma` canvas pixels, normalised by the
+    // blur of the frame's coverage) is feathered, its high band is taken from the one covering frame with the largest feather
+    // weight, so fine detail is not doubled where the frames overlap.  The taps are the centre-to-edge half of
+    // sift_hip_gauss_taps(sigma), whose radius is three sigma and may not exceed 16.  Throws std::invalid_argument for that and
+    // for what sift_hip_composite_twoband rejects.
+    Image2f composite_twoband(const std::vector<Image2f*>& frames, const std::vector<std::array<f32_t, 9>>& models, int out_w, int out_h, int origin_x = 0,
+                              int origin_y = 0, f32_t sigma = 5.0f, f32_t fill = 0.0f, bool bilinear = true, std::vector<uint16_t>* count = nullptr,
+                              const std::vector<f32_t>* gains = nullptr) {
+        if (frames.empty() || frames.size() != models.size()) throw std::invalid_argument("composite_twoband: one model per frame, at least one frame");
+        if (gains && gains->size() != frames.size()) throw std::invalid_argument("composite_twoband: one gain per frame");
+        std::vector<f32_t> taps(8192);
+        const int radius = sift_hip_gauss_taps(sigma, taps.data(), (int)taps.size());
+        if (radius < 0 || radius > 16) throw std::invalid_argument("composite_twoband: sigma must be >= 0 and give a radius (three sigma) of at most 16");
+        const size_t w = frames[0]->width(), h = frames[0]->height();
+        std::vector<f32_t> stack(frames.size() * w * h);
+        for (size_t k = 0; k < frames.size(); ++k) {
+            if (frames[k]->width() != w || frames[k]->height() != h) throw std::invalid_argument("composite_twoband: frames of one size");
+            std::copy(frames[k]->data(), frames[k]->data() + w * h, stack.begin() + k * w * h);
+        }
+        sift_hip_twoband_params prm{};
+        prm.out_w = out_w;
+        prm.out_h = out_h;
+        prm.origin_x = origin_x;
+        prm.origin_y = origin_y;
+        prm.fill = fill;
+        prm.interp = bilinear ? 1 : 0;
+        prm.radius = (uint8_t)radius;
+        Image2f out(out_w > 0 ? out_w : 0, out_h > 0 ? out_h : 0);
+        if (count) count->assign((size_t)out.width() * (size_t)out.height(), 0);
+        const int64_t offsets[2] = {0, (int64_t)frames.size()};
+        char err[512] = "";
+        const int rc = sift_hip_composite_twoband(_ctx, stack.data(), (int)frames.size(), (int)w, (int)h, 1, offsets, nullptr, models[0].data(), &prm,
+                                                  taps.data() + radius, gains ? gains->data() : nullptr, out.data(), count ? count->data() : nullptr, nullptr,
+                                                  err, sizeof(err));
+        if (rc == SIFT_HIP_EINVAL) throw std::invalid_argument(err);
+        if (rc != SIFT_HIP_OK) throw std::runtime_error(err);
+        return out;
+    }
+
     // The overlap statistics (include/sift_hip.h, "overlap statistics") of `frames` (at most 32, all of one size) placed as for
     // composite(): stats = 4 x 32 x 32 sums over the canvas pixels that frames i and j both cover - N (pixels), S (q_i), SS
     // (q_i^2), X (q_i q_j), q the 8-bit intensity round(value * scale) - and one gain per frame (Brown and Lowe's gain

@@ -617,6 +617,39 @@ int sift_hip_composite_homography_gains(sift_hip_ctx* ctx, const float* imgs, in
                                         const sift_hip_composite_params* params, const float* gains, float* out, uint16_t* count,
                                         int64_t* tiles, char* err, int errlen);
 
+/* ---- two-band compositor (an extension) -------------------------------------------------------------------
+ * The compositor's feather blend mixes every frequency over the whole overlap: with the few pixels of registration error a
+ * verified homography leaves, fine detail is doubled there.  Burt and Adelson's (1983) remedy with two bands, as Brown and Lowe
+ * (2007, section 7) apply it after gain compensation: each job's low band - its warped values under a separable blur of radius
+ * R, normalised by the blur of its coverage - is feathered, and its high band - value minus low band - is taken from the ONE
+ * covering job with the largest feather weight.  Canvases, jobs, offsets, src, models, origin, fill, interp, gains and count
+ * are the compositor's.  sift_amd/csrc/twoband_math.h defines every bit; the kernel and a plain host loop
+ * (hostmath_composite_twoband) compile it.  taps holds R + 1 floats k[0 .. R], k[d] the weight at offsets +d and -d.  For job j
+ * and ANY lattice point q, inside the canvas or not, with t_j the (gained) warped value where covered, else +0.0f, and m_j 1.0f
+ * where covered, else 0.0f: rs_j(X, Y) = the chain acc = +0.0f; dx = -R .. R ascending: acc = fmaf(k[|dx|], t_j(X + dx, Y), acc),
+ * ls_j(X, Y) = the same chain over dy on rs_j(X, Y + dy), rn_j and ln_j likewise from m_j; where covered L = ls / ln and
+ * H = t - L.  Canvas pixel, over its covering jobs in order: wgt = the feather weight, lacc = fmaf(wgt, L, lacc), wsum = wsum +
+ * wgt, cnt += 1, and the first covering job or wgt > best (strict) sets best = wgt, high = H  -> lacc / wsum + high; cnt == 0:
+ * fill.  A lattice point's value depends on the inputs alone: a cropped canvas is the crop of the larger one, bit for bit, and
+ * the result does not depend on `path`, tiles or the launch.  R = 0 with k = {1} is the feather blend. */
+typedef struct sift_hip_twoband_params {
+    int32_t out_w, out_h;        /* > 0 */
+    int32_t origin_x, origin_y;  /* as for the compositor */
+    float fill;
+    uint8_t interp;              /* 0 nearest, 1 bilinear; above: EINVAL */
+    uint8_t path;                /* 0: the library chooses per tile and job; 1: ln is formed from the coverage everywhere (same bits; measurement and tests) */
+    uint8_t radius;              /* R, 0 .. 16; above: EINVAL */
+    uint8_t reserved;            /* zero */
+} sift_hip_twoband_params;       /* 24 bytes */
+/* Memory kinds, scratch memory, stream and "not while a batch is in flight" as for sift_hip_composite_homography; taps is a
+ * host array, gains (n_jobs floats, host or device memory) may be NULL: none.  tiles (host, may be NULL): (tile, job) visits
+ * [0] on the general path, [1] on the constant-norm path (the job covers the tile's whole window: ln is one number), [2]
+ * skipped because no pixel of the tile was covered.  SIFT_HIP_EINVAL for the compositor's conditions, the lattice limit taken on
+ * the canvas widened by R on every side, a radius above 16, a tap that is not finite or < 0, or k[0] < 2^-12. */
+int sift_hip_composite_twoband(sift_hip_ctx* ctx, const float* imgs, int n_imgs, int w, int h, int n_canvases, const int64_t* offsets,
+                               const int32_t* src, const float* models, const sift_hip_twoband_params* params, const float* taps,
+                               const float* gains, float* out, uint16_t* count, int64_t* tiles, char* err, int errlen);
+
 /* ---- overlap statistics and gain compensation (an extension) ------------------------------------------------
  * The photometric statistics of every pair of a canvas's jobs where both cover the canvas, without writing a canvas: the input
  * of gain compensation (Brown and Lowe 2007, section 6) and of the zero-mean normalised cross-correlation of a registered pair.

@@ -45,6 +45,7 @@ SYMBOLS = [
     "sift_hip_result_localize", "sift_hip_localize_points",
     "sift_hip_warp_homography", "sift_hip_composite_homography",
     "sift_hip_composite_homography_gains", "sift_hip_overlap_stats",
+    "sift_hip_composite_twoband",
 ]
 
 
@@ -81,6 +82,15 @@ class CompositeParams(C.Structure):
 
 
 COMPOSITE_BLEND = {"first": 0, "mean": 1, "feather": 2}
+
+
+class TwobandParams(C.Structure):
+    _fields_ = [("out_w", C.c_int32), ("out_h", C.c_int32), ("origin_x", C.c_int32), ("origin_y", C.c_int32), ("fill", C.c_float),
+                ("interp", C.c_uint8), ("path", C.c_uint8), ("radius", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+TWOBAND_MAX_RADIUS = 16
+TWOBAND_TILE = (64, 32)   # (w, h) of the canvas tile a workgroup owns: kTwobandTileW, kTwobandTileH of csrc/twoband_kernels.h
 
 
 class OverlapParams(C.Structure):
@@ -271,5 +281,7 @@ def load():
     L.sift_hip_composite_homography_gains.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, C.POINTER(CompositeParams), vp, vp, vp, vp, cs, ci]
     # imgs, models, stats, gains and status: host or device memory; offsets and src: host arrays (src: or None)
     L.sift_hip_overlap_stats.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, C.POINTER(OverlapParams), vp, vp, vp, cs, ci]
+    # the compositor's arguments with taps (a host array) and gains (host or device memory, or None) before out
+    L.sift_hip_composite_twoband.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, C.POINTER(TwobandParams), vp, vp, vp, vp, vp, cs, ci]
     _lib = L
     return L

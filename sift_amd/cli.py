@@ -6,7 +6,7 @@ overlay :59-76) on top of the GPU path — SURVEY.md §8(f) rows 1-3.
     python -m sift_amd.cli -i a.pgm --match b.pgm --u8 [--verify ...]                (8-bit descriptors, integer distances)
     python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--iterations 2048] [--threshold 3] [--seed 0] [--refine 0] [--model homography|fundamental] [--refit N] [--localize]   (... and inliers.txt)
     python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--refine N] --warp out.png   (... and b registered onto a: the homography warp)
-    python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--refine N] --mosaic out.png [--blend first|mean|feather] [--gain]   (... and both frames on the canvas that holds them: the compositor)
+    python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--refine N] --mosaic out.png [--blend first|mean|feather|twoband [--band-sigma S]] [--gain]   (... and both frames on the canvas that holds them: the compositor)
     python -m sift_amd.cli -i a.pgm --match b.pgm --verify --guided [--guided-ratio R]   (... and guided.txt: the matches again, under the verified model)
 
 Image ingest follows Vigra's scalar import: band 0 of multi-band files, values unscaled.  PGM,
@@ -161,7 +161,10 @@ def main(argv=None) -> int:
     ap.add_argument("--mosaic", metavar="PNG",
                     help="with --verify (a homography; both images of one size): the image and IMG2 blended on the canvas that holds both "
                          "frames, written as PNG like --warp (black where neither reaches)")
-    ap.add_argument("--blend", choices=["first", "mean", "feather"], default="feather", help="how --mosaic blends where the frames overlap")
+    ap.add_argument("--blend", choices=["first", "mean", "feather", "twoband"], default="feather",
+                    help="how --mosaic blends where the frames overlap; twoband: low frequencies feathered, fine detail from one frame")
+    ap.add_argument("--band-sigma", type=float, default=5.0, metavar="S",
+                    help="with --blend twoband: the sigma, in canvas pixels, of the blur that splits the two bands (at most 16 / 3)")
     ap.add_argument("--gain", action="store_true",
                     help="with --mosaic: solve one gain per frame from the frames' overlap first (gain compensation) and blend the gained frames")
     ap.add_argument("--u8", action="store_true",
@@ -261,7 +264,10 @@ def main(argv=None) -> int:
                     if args.gain:
                         stats, gains, _ = sift.ctx.overlap_stats(frames, jobs, out_shape=shape, origin=(ox, oy), gains=True)
                         print(f"gains {' '.join(f'{g:.4f}' for g in gains)}; ZNCC over the overlap {sift.ctx.overlap_zncc(stats[0], len(jobs))[0, -1]:.4f}")
-                    pic, cover = sift.ctx.composite_homography(frames, jobs, out_shape=shape, origin=(ox, oy), blend=args.blend, count=True, gains=gains)
+                    if args.blend == "twoband":
+                        pic, cover = sift.ctx.composite_twoband(frames, jobs, out_shape=shape, origin=(ox, oy), sigma=args.band_sigma, count=True, gains=gains)
+                    else:
+                        pic, cover = sift.ctx.composite_homography(frames, jobs, out_shape=shape, origin=(ox, oy), blend=args.blend, count=True, gains=gains)
                     grey = np.clip(np.rint(pic[0]), 0, 255).astype(np.uint8)
                     _err_call(_lib.load().sift_hip_png_write_bgr8, args.mosaic.encode(), np.ascontiguousarray(np.repeat(grey[:, :, None], 3, axis=2)).reshape(-1), shape[1], shape[0])
                     print(f"{args.img} + {args.match} -> {args.mosaic} ({shape[1]} x {shape[0]}, origin {ox}, {oy}; {int((cover == 2).sum())} pixels under both)")

@@ -23,6 +23,7 @@
 #include "ransac_kernels.h"
 #include "warp_kernels.h"
 #include "composite_kernels.h"
+#include "twoband_kernels.h"
 #include "overlap_kernels.h"
 
 using namespace sift_hip;
@@ -213,6 +214,7 @@ struct sift_hip_ctx {
     sift_hip::RansacState* ransac_state = nullptr; // the same for the geometric verification (ransac.cpp)
     sift_hip::WarpState* warp_state = nullptr;     // the same for the homography warp (warp.cpp)
     sift_hip::CompositeState* composite_state = nullptr;   // the same for the compositor (composite.cpp)
+    sift_hip::TwobandState* twoband_state = nullptr;       // the same for the two-band compositor (twoband.cpp)
     sift_hip::OverlapState* overlap_state = nullptr;       // and for the overlap statistics (overlap.cpp)
     // sub-pixel localisation (sift_hip_result_localize): the records and their (x, y) of the last batch, the images' row offsets
     DevBuf d_loc, d_loc_xy, d_loc_row0;
@@ -1306,6 +1308,7 @@ void match_set_err(char* err, int errlen, const char* msg) { set_err(err, errlen
 RansacState** ransac_ctx_state(sift_hip_ctx* c) { return &c->ransac_state; }
 WarpState** warp_ctx_state(sift_hip_ctx* c) { return &c->warp_state; }
 CompositeState** composite_ctx_state(sift_hip_ctx* c) { return &c->composite_state; }
+TwobandState** twoband_ctx_state(sift_hip_ctx* c) { return &c->twoband_state; }
 OverlapState** overlap_ctx_state(sift_hip_ctx* c) { return &c->overlap_state; }
 bool ransac_ctx_subpixel(sift_hip_ctx* c) { return c->plan.params.subpixel != 0; }
 const float* localize_ctx_xy(sift_hip_ctx* c) { return (c->have_result && c->loc_use) ? c->d_loc_xy.as<float>() : nullptr; }
@@ -1360,6 +1363,7 @@ int sift_hip_create(int device, sift_hip_ctx** out, char* err, int errlen) {
                 tu_touch_localize(c->stream);
                 tu_touch_warp(c->stream);
                 tu_touch_composite(c->stream);
+                tu_touch_twoband(c->stream);
                 tu_touch_overlap(c->stream);
                 SIFT_HIP_CHECK(hipGetLastError());
                 SIFT_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -1380,6 +1384,7 @@ void sift_hip_destroy(sift_hip_ctx* c) {
     ransac_state_free(c->ransac_state);
     warp_state_free(c->warp_state);
     composite_state_free(c->composite_state);
+    twoband_state_free(c->twoband_state);
     overlap_state_free(c->overlap_state);
     ApiGuard api;
     for (DevBuf* b : {&c->arena, &c->d_plan, &c->d_taps, &c->d_luts, &c->d_taps16, &c->d_input, &c->d_input_u8, &c->d_sparse_rec, &c->d_sparse_val, &c->d_base, &c->d_tmp, &c->d_tmp2,

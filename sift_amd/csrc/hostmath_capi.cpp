@@ -716,3 +716,57 @@ void hostmath_overlap_stats(const float* imgs, int w, int h, int n_canvases, con
     }
 }
 }
+
+// ---- two-band compositor (twoband_math.h): the plain loop ----------------------------------------------------------
+#include <vector>
+
+#include "twoband_math.h"
+
+extern "C" {
+// canvas c: jobs offsets[c] .. offsets[c + 1] - 1 in order -> out[c] (out_h x out_w) and, unless null, count[c].  Job after job:
+// t and m on the canvas widened by R on every side, rs and rn on the canvas widened by R above and below, then every canvas
+// pixel's bands into its accumulator.  The caller keeps the header's conditions on radius and taps.
+void hostmath_composite_twoband(const float* imgs, int w, int h, int n_canvases, const int64_t* offsets, const int32_t* src, const float* models,
+                                const sift_hip_twoband_params* p, const float* taps, const float* gains, float* out, uint16_t* count) {
+    using namespace sift_hip;
+    const int R = p->radius, ow = p->out_w, oh = p->out_h, pw = ow + 2 * R, ph = oh + 2 * R;
+    const size_t px = (size_t)ow * (size_t)oh;
+    std::vector<float> t((size_t)pw * ph), m((size_t)pw * ph), rs((size_t)ow * ph), rn((size_t)ow * ph), wgt(px);
+    std::vector<TwobandAcc> acc(px);
+    for (int c = 0; c < n_canvases; ++c) {
+        for (size_t o = 0; o < px; ++o) acc[o] = TwobandAcc{0.0f, 0.0f, 0.0f, 0.0f, 0u};
+        for (int64_t j = offsets[c]; j < offsets[c + 1]; ++j) {
+            float mdl[9];
+            for (int k = 0; k < 9; ++k) mdl[k] = models[9 * (size_t)j + k];
+            const float* s = imgs + (size_t)(src ? src[j] : j) * (size_t)w * (size_t)h;
+            for (int y = 0; y < ph; ++y)
+                for (int x = 0; x < pw; ++x) {   // the lattice point (x - R + origin_x, y - R + origin_y)
+                    float val, wg;
+                    const bool cov = twoband_sample(s, w, h, mdl, (float)(x - R + p->origin_x), (float)(y - R + p->origin_y), p->interp, gains ? gains + j : nullptr, val, wg);
+                    t[(size_t)y * pw + x] = val;
+                    m[(size_t)y * pw + x] = cov ? 1.0f : 0.0f;
+                    if (x >= R && x < R + ow && y >= R && y < R + oh) wgt[(size_t)(y - R) * ow + (x - R)] = wg;
+                }
+            for (int y = 0; y < ph; ++y)
+                for (int x = 0; x < ow; ++x) {
+                    const size_t at = (size_t)y * pw + (x + R);
+                    rs[(size_t)y * ow + x] = twoband_chain(taps, R, [&](int d) { return t[at + d]; });
+                    rn[(size_t)y * ow + x] = twoband_chain(taps, R, [&](int d) { return m[at + d]; });
+                }
+            for (int y = 0; y < oh; ++y)
+                for (int x = 0; x < ow; ++x) {
+                    const size_t q = (size_t)(y + R) * pw + (x + R);
+                    if (m[q] == 0.0f) continue;
+                    const size_t at = (size_t)(y + R) * ow + x;
+                    const float ls = twoband_chain(taps, R, [&](int d) { return rs[at + (ptrdiff_t)d * ow]; });
+                    const float ln = twoband_chain(taps, R, [&](int d) { return rn[at + (ptrdiff_t)d * ow]; });
+                    twoband_add(acc[(size_t)y * ow + x], wgt[(size_t)y * ow + x], t[q], ls, ln);
+                }
+        }
+        for (size_t o = 0; o < px; ++o) {
+            out[(size_t)c * px + o] = twoband_result(acc[o], p->fill);
+            if (count) count[(size_t)c * px + o] = (uint16_t)acc[o].cnt;
+        }
+    }
+}
+}

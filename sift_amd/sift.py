@@ -914,16 +914,9 @@ class Context:
         return got[0] if len(got) == 1 else got
 
     # ---- compositor (include/sift_hip.h, "compositor") ---------------------------------------------------------
-    def composite_homography(self, imgs, models, offsets=None, src=None, out_shape=None, origin=(0, 0), fill=0.0, interp="bilinear", blend="feather",
-                             path=0, out=None, count=False, want_tiles=False, shape=None, gains=None):
-        """sift_hip_composite_homography: canvas c accumulates jobs offsets[c] .. offsets[c + 1] - 1 in order, job j being image
-        src[j] (None: image j) under models[j] as in warp_homography -> (out[, count][, tiles]): out [n_canvases, out_h, out_w]
-        float32, one picture per canvas; count uint16, the jobs that cover each pixel (0: `fill`); tiles = (staged, direct,
-        skipped) (tile, job) visits with `want_tiles`.  `offsets` None: one canvas of all jobs.  `blend`: "first" (the first
-        covering job's value), "mean" or "feather" (weights: distance to the source frame's border plus one).  `imgs`, `models`,
-        `out_shape`, `origin`, `interp`, `path`, `shape` as in warp_homography; `out`, and `count` when it is not a bool: where
-        a result goes (returned as given).  `gains` (sift_hip_composite_homography_gains): one float per job, numbers, a tensor
-        or an address - a covering job's value is multiplied by its gain (overlap_stats solves them); None: no gains."""
+    @staticmethod
+    def _composite_inputs(name, imgs, models, offsets, src, out_shape, interp, shape, gains):
+        """What composite_homography and composite_twoband share -> (imgs, shape, models, n_jobs, offsets, src, (oh, ow), gains)."""
         if isinstance(imgs, np.ndarray):
             imgs = np.ascontiguousarray(imgs, np.float32)
             imgs = imgs[None] if imgs.ndim == 2 else imgs
@@ -931,11 +924,9 @@ class Context:
         elif shape is None:
             shape = tuple(imgs.shape)   # a tensor
         if len(shape) != 3:
-            raise ValueError("composite_homography: imgs is [n, h, w]")
+            raise ValueError(name + ": imgs is [n, h, w]")
         if interp not in _lib.WARP_INTERP:
-            raise ValueError('composite_homography: interp must be "nearest" or "bilinear"')
-        if blend not in _lib.COMPOSITE_BLEND:
-            raise ValueError('composite_homography: blend must be "first", "mean" or "feather"')
+            raise ValueError(name + ': interp must be "nearest" or "bilinear"')
         if isinstance(models, np.ndarray) and models.dtype.names:
             models = models["h"]
         if isinstance(models, (np.ndarray, list, tuple)):
@@ -946,11 +937,31 @@ class Context:
         if src is not None:
             src = np.ascontiguousarray(src, np.int32).reshape(-1)
             if src.size != n_jobs:
-                raise ValueError("composite_homography: one src index per model")
+                raise ValueError(name + ": one src index per model")
         offsets = np.array([0, n_jobs], np.int64) if offsets is None else np.ascontiguousarray(offsets, np.int64).reshape(-1)
         if offsets.size < 1 or offsets[-1] != n_jobs:
-            raise ValueError("composite_homography: offsets has one entry per canvas and one more, the last being the number of models")
+            raise ValueError(name + ": offsets has one entry per canvas and one more, the last being the number of models")
         oh, ow = (int(shape[1]), int(shape[2])) if out_shape is None else (int(out_shape[0]), int(out_shape[1]))
+        if isinstance(gains, (np.ndarray, list, tuple)):
+            gains = np.ascontiguousarray(gains, np.float32).reshape(-1)
+            if gains.size != n_jobs:
+                raise ValueError(name + ": one gain per model")
+        return imgs, shape, models, n_jobs, offsets, src, (oh, ow), gains
+
+    def composite_homography(self, imgs, models, offsets=None, src=None, out_shape=None, origin=(0, 0), fill=0.0, interp="bilinear", blend="feather",
+                             path=0, out=None, count=False, want_tiles=False, shape=None, gains=None):
+        """sift_hip_composite_homography: canvas c accumulates jobs offsets[c] .. offsets[c + 1] - 1 in order, job j being image
+        src[j] (None: image j) under models[j] as in warp_homography -> (out[, count][, tiles]): out [n_canvases, out_h, out_w]
+        float32, one picture per canvas; count uint16, the jobs that cover each pixel (0: `fill`); tiles = (staged, direct,
+        skipped) (tile, job) visits with `want_tiles`.  `offsets` None: one canvas of all jobs.  `blend`: "first" (the first
+        covering job's value), "mean" or "feather" (weights: distance to the source frame's border plus one).  `imgs`, `models`,
+        `out_shape`, `origin`, `interp`, `path`, `shape` as in warp_homography; `out`, and `count` when it is not a bool: where
+        a result goes (returned as given).  `gains` (sift_hip_composite_homography_gains): one float per job, numbers, a tensor
+        or an address - a covering job's value is multiplied by its gain (overlap_stats solves them); None: no gains."""
+        if blend not in _lib.COMPOSITE_BLEND:
+            raise ValueError('composite_homography: blend must be "first", "mean" or "feather"')
+        imgs, shape, models, n_jobs, offsets, src, (oh, ow), gains = self._composite_inputs("composite_homography", imgs, models, offsets, src, out_shape, interp,
+                                                                                            shape, gains)
         prm = _lib.CompositeParams(ow, oh, int(origin[0]), int(origin[1]), float(fill), _lib.WARP_INTERP[interp], _lib.COMPOSITE_BLEND[blend], int(path) & 0xff)
         size = (offsets.size - 1, max(oh, 0), max(ow, 0))   # a bad size: the call says so
         res = np.zeros(size, np.float32) if out is None else out
@@ -962,11 +973,44 @@ class Context:
         if gains is None:
             rc = self._L.sift_hip_composite_homography(*head, self._addr(res), self._addr(cnt), self._addr(tiles), err, 512)
         else:
-            if isinstance(gains, (np.ndarray, list, tuple)):
-                gains = np.ascontiguousarray(gains, np.float32).reshape(-1)
-                if gains.size != n_jobs:
-                    raise ValueError("composite_homography: one gain per model")
             rc = self._L.sift_hip_composite_homography_gains(*head, self._addr(gains), self._addr(res), self._addr(cnt), self._addr(tiles), err, 512)
+        if rc:
+            _raise(rc, err)
+        got = (res,) + ((cnt,) if cnt is not None else ()) + ((tuple(int(t) for t in tiles),) if want_tiles else ())
+        return got[0] if len(got) == 1 else got
+
+    # ---- two-band compositor (include/sift_hip.h, "two-band compositor") ---------------------------------------
+    @staticmethod
+    def band_taps(sigma: float):
+        """The taps composite_twoband forms from `sigma`: the centre-to-edge half of gauss_taps(sigma) -> float32 [radius + 1]."""
+        r, taps = gauss_taps(float(sigma))
+        if r > _lib.TWOBAND_MAX_RADIUS:
+            raise ValueError(f"composite_twoband: sigma {sigma} gives a radius of {r}, above {_lib.TWOBAND_MAX_RADIUS}")
+        return np.ascontiguousarray(taps[r:], np.float32)
+
+    def composite_twoband(self, imgs, models, offsets=None, src=None, out_shape=None, origin=(0, 0), fill=0.0, interp="bilinear", sigma=5.0, taps=None,
+                          path=0, out=None, count=False, want_tiles=False, shape=None, gains=None):
+        """sift_hip_composite_twoband: composite_homography's canvases and jobs blended in two frequency bands (Burt and Adelson)
+        -> (out[, count][, tiles]).  A job's low band - its warped values under the separable blur `taps`, normalised by the blur
+        of its coverage - is feathered; its high band, value minus low band, comes from the one covering job with the largest
+        feather weight, so fine detail is not doubled where frames overlap.  `taps`: radius + 1 numbers, the weight at offsets
+        +d and -d, radius at most 16; None: band_taps(`sigma`), whose radius is three sigma (sigma <= 16 / 3).  tiles =
+        (general, constant-norm, skipped) (tile, job) visits with `want_tiles`; `path` 1: every visit takes the general path
+        (the same bits).  Everything else as in composite_homography."""
+        imgs, shape, models, n_jobs, offsets, src, (oh, ow), gains = self._composite_inputs("composite_twoband", imgs, models, offsets, src, out_shape, interp,
+                                                                                            shape, gains)
+        taps = self.band_taps(sigma) if taps is None else np.ascontiguousarray(taps, np.float32).reshape(-1)
+        if not 1 <= taps.size <= _lib.TWOBAND_MAX_RADIUS + 1:
+            raise ValueError(f"composite_twoband: taps are radius + 1 numbers, radius 0 .. {_lib.TWOBAND_MAX_RADIUS}")
+        prm = _lib.TwobandParams(ow, oh, int(origin[0]), int(origin[1]), float(fill), _lib.WARP_INTERP[interp], int(path) & 0xff, taps.size - 1)
+        size = (offsets.size - 1, max(oh, 0), max(ow, 0))   # a bad size: the call says so
+        res = np.zeros(size, np.float32) if out is None else out
+        cnt = (np.zeros(size, np.uint16) if count else None) if isinstance(count, bool) else count
+        tiles = np.zeros(3, np.int64) if want_tiles else None
+        err = C.create_string_buffer(512)
+        rc = self._L.sift_hip_composite_twoband(self._h, self._addr(imgs), int(shape[0]), int(shape[2]), int(shape[1]), offsets.size - 1, self._addr(offsets),
+                                                self._addr(src), self._addr(models), C.byref(prm), self._addr(taps), self._addr(gains), self._addr(res),
+                                                self._addr(cnt), self._addr(tiles), err, 512)
         if rc:
             _raise(rc, err)
         got = (res,) + ((cnt,) if cnt is not None else ()) + ((tuple(int(t) for t in tiles),) if want_tiles else ())
@@ -1282,7 +1326,7 @@ class Sift:
 
     def mosaic(self, imgs, ref: int = 0, pairs=None, blend: str = "feather", ratio: float = 0.8, cross_check: bool = False, iterations: int = 2048,
                threshold: float = 3.0, seed: int = 0, refine: int = 0, quantized: bool = False, fill: float = 0.0, interp: str = "bilinear",
-               chain: bool = False, canvas=None, gain: bool = False, scale: float = 1.0):
+               chain: bool = False, canvas=None, gain: bool = False, scale: float = 1.0, band_sigma: float = 5.0):
         """A mosaic or a stack (an extension): calculate() on every frame of `imgs` [n, h, w], verify() on every pair (query,
         train) and Context.composite_homography of the placed frames on one canvas in frame `ref`'s coordinates -> (models,
         canvas, count, origin): one homography record per pair, the picture [out_h, out_w], the number of frames that cover each
@@ -1294,7 +1338,8 @@ class Sift:
         corners through its inverse model, each side clipped to 4 x the frame's larger side around frame `ref`; else (origin,
         shape) = ((x, y), (out_h, out_w)).  Bit for bit the composition of those calls.  `gain`: Context.overlap_stats(gains=True, scale=`scale`)
         on the same canvas first, the gains given to the compositor -> (models, canvas, count, origin, gains, zncc): one gain
-        per placed frame in job order and Context.overlap_zncc of the placed frames (at most 32)."""
+        per placed frame in job order and Context.overlap_zncc of the placed frames (at most 32).  `blend` "twoband":
+        Context.composite_twoband(sigma=`band_sigma`) in the compositor's place, also together with `gain`."""
         imgs = np.asarray(imgs)
         if imgs.ndim != 3:
             raise ValueError("mosaic: imgs is [n, h, w]")
@@ -1320,11 +1365,16 @@ class Sift:
             origin, shape = self.mosaic_canvas(job_models[1:], w, h)
         else:
             origin, shape = (int(canvas[0][0]), int(canvas[0][1])), (int(canvas[1][0]), int(canvas[1][1]))
+        def compose(gains):
+            if blend == "twoband":
+                return self.ctx.composite_twoband(imgs.astype(np.float32), job_models, None, src, shape, origin, fill, interp, band_sigma, count=True, gains=gains)
+            return self.ctx.composite_homography(imgs.astype(np.float32), job_models, None, src, shape, origin, fill, interp, blend, count=True, gains=gains)
+
         if gain:
             stats, gains, _ = self.ctx.overlap_stats(imgs.astype(np.float32), job_models, None, src, shape, origin, scale, interp, gains=True)
-            out, count = self.ctx.composite_homography(imgs.astype(np.float32), job_models, None, src, shape, origin, fill, interp, blend, count=True, gains=gains)
+            out, count = compose(gains)
             return models, out[0], count[0], origin, gains, self.ctx.overlap_zncc(stats[0], len(src))
-        out, count = self.ctx.composite_homography(imgs.astype(np.float32), job_models, None, src, shape, origin, fill, interp, blend, count=True)
+        out, count = compose(None)
         return models, out[0], count[0], origin
 
     def refine_fundamental(self, points_a, points_b, recs, model, threshold: float = 3.0, rounds: int = 2, localized=None):
