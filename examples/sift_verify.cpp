@@ -3,11 +3,13 @@
 // or, with model=fundamental, sift::Matcher::verify_fundamental(): a seven-point fundamental matrix, the model for two views of a
 // general scene.  inliers.txt holds the lines of matches.txt that agree with the model.
 //   g++ -std=c++17 -pthread -Iinclude examples/sift_verify.cpp -Lsift_amd/lib -lsift_hip -Wl,-rpath,$PWD/sift_amd/lib -o sift_verify
-//   ./sift_verify a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [refine=0] [model=homography|fundamental] [refit=-1] [localize=0] [warp|mosaic out.pgm [gain] [twoband]]
+//   ./sift_verify a.pgm b.pgm [octaves=4] [dogsPerEpoch=3] [ratio=0.8] [crossCheck=0] [iterations=2048] [threshold=3] [seed=0] [refine=0] [model=homography|fundamental] [refit=-1] [localize=0] [warp|mosaic out.pgm [gain] [twoband]] [align N]
 //   ... warp out.pgm (with model=homography): b registered onto a under the verified model (sift::Matcher::warp), as an 8-bit PGM
 //   ... mosaic out.pgm (likewise; a and b of one size): both frames feathered on the canvas that holds them (sift::Matcher::composite)
 //   ... mosaic out.pgm gain: the frames' gains are solved from their overlap first (sift::Matcher::overlap) and applied
 //   ... mosaic out.pgm twoband: blended in two frequency bands of sigma 5 instead (sift::Matcher::composite_twoband), also after gain
+//   ... align N (with model=homography, a and b of one size; last, or alone in place of warp|mosaic): the verified model refined on the
+//       pixels by at most N Gauss-Newton steps (sift::Matcher::align) before it is printed, warped or composed
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -42,7 +44,7 @@ static void write_matches(const char* path, const std::vector<sift::Match>& matc
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::cerr << "usage: " << argv[0]
-                  << " a.{pgm,ppm,png,jpg} b.{...} [octaves] [dogsPerEpoch] [ratio] [crossCheck] [iterations] [threshold] [seed] [refine] [homography|fundamental] [refit] [localize] [warp|mosaic out.pgm]\n";
+                  << " a.{pgm,ppm,png,jpg} b.{...} [octaves] [dogsPerEpoch] [ratio] [crossCheck] [iterations] [threshold] [seed] [refine] [homography|fundamental] [refit] [localize] [warp|mosaic out.pgm [gain] [twoband]] [align N]\n";
         return 1;
     }
     const u16_t octaves = argc > 3 ? (u16_t)std::atoi(argv[3]) : 4;
@@ -67,12 +69,15 @@ int main(int argc, char** argv) {
     // "mosaic out.pgm": a under the identity and b under the verified homography on one canvas
     const std::string mosaic_file = argc > 15 && std::string(argv[14]) == "mosaic" ? argv[15] : "";
     bool mosaic_gain = false, mosaic_twoband = false;   // "gain" and "twoband" after the file, in either order
-    for (int k = 16; k < argc && k < 18; ++k) {
+    int align_rounds = 0;   // "align N" after everything else
+    for (int k = 16; k < argc; ++k) {
         mosaic_gain |= std::string(argv[k]) == "gain";
         mosaic_twoband |= std::string(argv[k]) == "twoband";
     }
-    if ((!warp_file.empty() || !mosaic_file.empty()) && model_name != "homography") {
-        std::cerr << "warp and mosaic are for model=homography\n";
+    for (int k = 14; k + 1 < argc; ++k)
+        if (std::string(argv[k]) == "align") align_rounds = std::atoi(argv[k + 1]);
+    if ((!warp_file.empty() || !mosaic_file.empty() || align_rounds) && model_name != "homography") {
+        std::cerr << "warp, mosaic and align are for model=homography\n";
         return 1;
     }
     if (refit >= 0 && model_name != "fundamental") {
@@ -109,7 +114,7 @@ int main(int argc, char** argv) {
             }
             return 0;
         }
-        const sift::Homography model = matcher.verify(a, b, matches, iterations, threshold, seed, false, refine);
+        sift::Homography model = matcher.verify(a, b, matches, iterations, threshold, seed, false, refine);
         write_matches("matches.txt", matches, nullptr);
         write_matches("inliers.txt", matches, &model.inlier);
         std::cout << a.size() << " and " << b.size() << " interest points, " << matches.size() << " matches -> matches.txt, " << model.inliers
@@ -118,6 +123,22 @@ int main(int argc, char** argv) {
         if (model.iteration < 0) {
             std::cout << "no homography\n";
         } else {
+            for (int r = 0; r < 3; ++r) std::printf("H %.9g %.9g %.9g\n", (double)model.h[3 * r], (double)model.h[3 * r + 1], (double)model.h[3 * r + 2]);
+        }
+        if (align_rounds && model.iteration >= 0) {   // the model refined on the pixels; what follows takes the refined one
+            char err[512] = "";
+            int w = 0, h = 0, wb = 0, hb = 0;
+            if (sift_hip_image_info(argv[1], &w, &h, nullptr, nullptr, err, sizeof(err)) != SIFT_HIP_OK ||
+                sift_hip_image_info(argv[2], &wb, &hb, nullptr, nullptr, err, sizeof(err)) != SIFT_HIP_OK)
+                throw std::runtime_error(err);
+            if (w != wb || h != hb) throw std::runtime_error("align: the two images must have one size");
+            sift::Image2f fa(w, h), fb(w, h);
+            if (sift_hip_image_read_band0(argv[1], fa.data(), (long long)w * h, err, sizeof(err)) != SIFT_HIP_OK ||
+                sift_hip_image_read_band0(argv[2], fb.data(), (long long)w * h, err, sizeof(err)) != SIFT_HIP_OK)
+                throw std::runtime_error(err);
+            const sift_hip_alignment al = matcher.align(fa, fb, model.h, align_rounds);
+            std::printf("aligned %d rounds (status %d): rms %.4f -> %.4f over %d pixels, gain %.4f, bias %.3f\n", al.rounds, al.status, (double)al.rms0,
+                        (double)al.rms, al.pixels, (double)al.gain, (double)al.bias);
             for (int r = 0; r < 3; ++r) std::printf("H %.9g %.9g %.9g\n", (double)model.h[3 * r], (double)model.h[3 * r + 1], (double)model.h[3 * r + 2]);
         }
         if (!warp_file.empty()) {   // no homography: the all-zero model covers nothing, the picture is black

@@ -329,6 +329,35 @@ public:
         return r;
     }
 
+    // The direct alignment (include/sift_hip.h, "direct alignment"): the nine floats `h` (query to train, as verify() returns
+    // them) refined IN PLACE on the pixels of the two frames (of one size) by at most `rounds` (0 .. 8) Gauss-Newton steps on
+    // sum (query - gain train(H .) - bias)^2; the record says what was reached (h, gain, bias, rms0 -> rms, pixels, rounds,
+    // status SIFT_HIP_ALIGN_*).  Throws std::invalid_argument for what sift_hip_align_homography rejects.
+    sift_hip_alignment align(Image2f& query, Image2f& train, f32_t (&h)[9], int rounds = 4, int border = 2, int min_pixels = 256,
+                             f32_t damping = 0.0f) {
+        if (query.width() != train.width() || query.height() != train.height()) throw std::invalid_argument("align: frames of one size");
+        const size_t px = (size_t)query.width() * (size_t)query.height();
+        std::vector<f32_t> stack(2 * px);
+        std::copy(query.data(), query.data() + px, stack.begin());
+        std::copy(train.data(), train.data() + px, stack.begin() + px);
+        sift_hip_align_params prm{};
+        prm.rounds = rounds;
+        prm.border = border;
+        prm.min_pixels = min_pixels;
+        prm.damping = damping;
+        sift_hip_homography model{};
+        std::copy(h, h + 9, model.h);
+        sift_hip_alignment out{};
+        const int32_t pq = 0, pt = 1;
+        char err[512] = "";
+        const int rc = sift_hip_align_homography(_ctx, stack.data(), 2, (int)query.width(), (int)query.height(), 1, &pq, &pt, &prm, &model, &out, nullptr,
+                                                 err, sizeof(err));
+        if (rc == SIFT_HIP_EINVAL) throw std::invalid_argument(err);
+        if (rc != SIFT_HIP_OK) throw std::runtime_error(err);
+        std::copy(model.h, model.h + 9, h);
+        return out;
+    }
+
 private:
     // the image coordinates of point i of the query (side 0) or train (side 1) list
     void coords(const InterestPoint& p, int side, size_t i, f32_t scale, f32_t* xy) const {

@@ -682,6 +682,55 @@ int sift_hip_overlap_stats(sift_hip_ctx* ctx, const float* imgs, int n_imgs, int
                            const int32_t* src, const float* models, const sift_hip_overlap_params* params, int64_t* stats,
                            float* gains, uint8_t* status, char* err, int errlen);
 
+/* ---- direct alignment (an extension) -----------------------------------------------------------------------
+ * Refines a homography on the pixels themselves (Lucas-Kanade / Gauss-Newton on the intensities, after the feature-based
+ * estimate): for pair p, with Q = image pair_q[p], T = image pair_t[p] and H = models[p].h (query to train), at most `rounds`
+ * steps that lower  E = sum (Q(x) - gain T(H x) - bias)^2  over the eight free entries of H, the gain and the bias (start 1, 0).
+ * The sum runs over the query pixels x whose image H x lies inside T with four distinct bilinear taps (the warp's coverage
+ * test, u < w - 1, v < h - 1) and that lie `border` pixels inside the frame.  T(H x) is the warp's bilinear value; its gradient
+ * is the derivative of the same bilinear patch.  sift_amd/csrc/align_math.h defines every bit - the twelve columns per pixel in
+ * normalised coordinates, the 78 sums of their products in a fixed order (float chains of at most 16 pixels, then double), the
+ * step in double with the refit's elimination, the entry of the normalised model that stays fixed - and the kernels and a plain
+ * host loop (hostmath_align_homography) compile it.  A step is kept only while E / n does not rise; `rounds` steps take
+ * rounds + 1 passes over the pair, the last of which only evaluates.  status:
+ *   SIFT_HIP_ALIGN_OK          every round ran (rounds == params.rounds)
+ *   SIFT_HIP_ALIGN_NO_MODEL    models[p].iteration == -1: nothing is read or changed, h is the record's
+ *   SIFT_HIP_ALIGN_TOO_FEW     fewer than max(min_pixels, 1) pixels contribute
+ *   SIFT_HIP_ALIGN_NOT_FINITE  a sum or an updated parameter is not finite
+ *   SIFT_HIP_ALIGN_SINGULAR    a pivot of the 10 x 10 system is zero or not finite (a constant image)
+ *   SIFT_HIP_ALIGN_ROSE        a step raised E / n: it is undone and the rounds end
+ * Whatever the status, h, gain and bias are the last ACCEPTED model (the start when no step was), rms the root of its E / n,
+ * pixels its n (with TOO_FEW at the start: the n that was too small), rms0 the root of E / n at the start. */
+enum { SIFT_HIP_ALIGN_OK = 0, SIFT_HIP_ALIGN_NO_MODEL = 1, SIFT_HIP_ALIGN_TOO_FEW = 2, SIFT_HIP_ALIGN_NOT_FINITE = 3,
+       SIFT_HIP_ALIGN_SINGULAR = 4, SIFT_HIP_ALIGN_ROSE = 5 };
+typedef struct sift_hip_align_params {
+    int32_t rounds;       /* Gauss-Newton steps at most, 0 .. 8; 0 only evaluates */
+    int32_t border;       /* >= 0 and below half of either side */
+    int32_t min_pixels;   /* a pass with fewer contributing pixels stops the pair */
+    float damping;        /* the diagonal of J^T J is multiplied by 1 + damping; finite, >= 0 */
+    uint8_t path;         /* 0: 16 pixels a lane, rows without a contributing pixel in a wave are skipped; 1: every pixel is
+                             computed and masked (same bits; measurement and tests) */
+    uint8_t reserved[3];  /* zero */
+} sift_hip_align_params;  /* 20 bytes */
+typedef struct sift_hip_alignment {
+    float h[9];           /* row-major, divided by its entry of largest magnitude once a step was accepted */
+    float gain, bias;
+    float rms0, rms;      /* sqrt(E / n) at the start and of the returned model */
+    int32_t pixels;       /* n of the returned model */
+    int32_t rounds;       /* steps accepted */
+    int32_t status;
+} sift_hip_alignment;     /* 64 bytes */
+/* imgs (n_imgs x h x w), models (n_pairs records, in and out: h is rewritten with the returned model, the rest is kept) and out
+ * (n_pairs records) may each be host or device memory; pair_q and pair_t are host arrays; sums (host memory, may be NULL)
+ * receives n_pairs x 80 doubles, the 78 sums, the count and a zero of each pair's LAST pass (zeros for a pair without a model):
+ * for tests.  The passes are separate launches on the context's stream with no host synchronisation in between; scratch
+ * memory, stream and "not while a batch is in flight" as for the warp.  SIFT_HIP_EINVAL for a bad size (w, h above 2^22,
+ * n_pairs above 65535), rounds outside 0 .. 8, a damping that is negative or not finite, a border that is negative or
+ * 2 border >= min(w, h), a pair index outside the images, path above 1 or non-zero reserved bytes. */
+int sift_hip_align_homography(sift_hip_ctx* ctx, const float* imgs, int n_imgs, int w, int h, int n_pairs, const int32_t* pair_q,
+                              const int32_t* pair_t, const sift_hip_align_params* params, sift_hip_homography* models,
+                              sift_hip_alignment* out, double* sums, char* err, int errlen);
+
 /* ---- inspection of the last batch (parity tests) ------------------------------------------------ */
 /* kind: 0 gaussian (levels 0..D), 1 dog (0..D-1), 2 magnitude, 3 orientation (initial gradient
  * maps, sift.cpp:130-160, only for levels some keypoint scale selects; 0x0 otherwise). */

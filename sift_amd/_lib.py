@@ -45,7 +45,7 @@ SYMBOLS = [
     "sift_hip_result_localize", "sift_hip_localize_points",
     "sift_hip_warp_homography", "sift_hip_composite_homography",
     "sift_hip_composite_homography_gains", "sift_hip_overlap_stats",
-    "sift_hip_composite_twoband",
+    "sift_hip_composite_twoband", "sift_hip_align_homography",
 ]
 
 
@@ -99,6 +99,19 @@ class OverlapParams(C.Structure):
 
 
 OVERLAP_MAX_JOBS = 32
+
+
+class AlignParams(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("border", C.c_int32), ("min_pixels", C.c_int32), ("damping", C.c_float), ("path", C.c_uint8),
+                ("reserved", C.c_uint8 * 3)]
+
+
+# sift_hip_alignment: the result of the direct alignment of one pair
+ALIGNMENT_DTYPE = np.dtype([("h", "<f4", (9,)), ("gain", "<f4"), ("bias", "<f4"), ("rms0", "<f4"), ("rms", "<f4"), ("pixels", "<i4"),
+                            ("rounds", "<i4"), ("status", "<i4")])
+assert ALIGNMENT_DTYPE.itemsize == 64
+ALIGN_OK, ALIGN_NO_MODEL, ALIGN_TOO_FEW, ALIGN_NOT_FINITE, ALIGN_SINGULAR, ALIGN_ROSE = 0, 1, 2, 3, 4, 5
+ALIGN_SUMS = 80   # doubles per pair: the 78 sums, the pixel count, a zero
 
 
 class RansacParams(C.Structure):
@@ -283,5 +296,7 @@ def load():
     L.sift_hip_overlap_stats.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, C.POINTER(OverlapParams), vp, vp, vp, cs, ci]
     # the compositor's arguments with taps (a host array) and gains (host or device memory, or None) before out
     L.sift_hip_composite_twoband.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, C.POINTER(TwobandParams), vp, vp, vp, vp, vp, cs, ci]
+    # imgs, models (in and out) and out: host or device memory; pair_q, pair_t and sums: host arrays (sums: or None)
+    L.sift_hip_align_homography.argtypes = [vp, vp, ci, ci, ci, ci, i32p, i32p, C.POINTER(AlignParams), vp, vp, vp, cs, ci]
     _lib = L
     return L

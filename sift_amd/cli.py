@@ -7,6 +7,7 @@ overlay :59-76) on top of the GPU path — SURVEY.md §8(f) rows 1-3.
     python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--iterations 2048] [--threshold 3] [--seed 0] [--refine 0] [--model homography|fundamental] [--refit N] [--localize]   (... and inliers.txt)
     python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--refine N] --warp out.png   (... and b registered onto a: the homography warp)
     python -m sift_amd.cli -i a.pgm --match b.pgm --verify [--refine N] --mosaic out.png [--blend first|mean|feather|twoband [--band-sigma S]] [--gain]   (... and both frames on the canvas that holds them: the compositor)
+    python -m sift_amd.cli -i a.pgm --match b.pgm --verify --align N [--warp out.png | --mosaic out.png ...]   (... the homography refined on the pixels first: direct alignment)
     python -m sift_amd.cli -i a.pgm --match b.pgm --verify --guided [--guided-ratio R]   (... and guided.txt: the matches again, under the verified model)
 
 Image ingest follows Vigra's scalar import: band 0 of multi-band files, values unscaled.  PGM,
@@ -167,6 +168,10 @@ def main(argv=None) -> int:
                     help="with --blend twoband: the sigma, in canvas pixels, of the blur that splits the two bands (at most 16 / 3)")
     ap.add_argument("--gain", action="store_true",
                     help="with --mosaic: solve one gain per frame from the frames' overlap first (gain compensation) and blend the gained frames")
+    ap.add_argument("--align", type=int, default=0, metavar="N",
+                    help="with --verify (a homography; both images of one size): refine the verified model on the pixels by at most N (1 .. 8) "
+                         "Gauss-Newton steps (direct alignment) and print rms0 -> rms and the pixel count; --warp, --mosaic and --guided "
+                         "then take the refined model")
     ap.add_argument("--u8", action="store_true",
                     help="with --match: quantise the descriptors to 8 bits on the GPU and match by the integer distance (the distances "
                          "in matches.txt are integers)")
@@ -183,6 +188,10 @@ def main(argv=None) -> int:
         ap.error("--warp needs --verify with --model homography")
     if args.mosaic and not (args.verify and args.model == "homography"):
         ap.error("--mosaic needs --verify with --model homography")
+    if args.align and not (args.verify and args.model == "homography"):
+        ap.error("--align needs --verify with --model homography")
+    if not 0 <= args.align <= 8:
+        ap.error("--align must be 0 .. 8")
     if args.gain and not args.mosaic:
         ap.error("--gain needs --mosaic")
     if args.u8 and args.guided:
@@ -248,6 +257,14 @@ def main(argv=None) -> int:
                 elif model["iteration"] < 0:
                     print("no homography")
                 else:
+                    for r in range(3):
+                        print("H " + " ".join("%.9g" % float(v) for v in model["h"][3 * r:3 * r + 3]))
+                if args.align and model["iteration"] >= 0:   # what follows takes the refined model
+                    frames = np.stack([np.asarray(img, np.float32), read_image(args.match).astype(np.float32)])
+                    refined, res = sift.ctx.align_homography(frames, [(0, 1)], np.asarray(model).reshape(1), rounds=args.align)
+                    model = refined[0]
+                    print(f"aligned {int(res['rounds'][0])} rounds (status {int(res['status'][0])}): rms {float(res['rms0'][0]):.4f} -> "
+                          f"{float(res['rms'][0]):.4f} over {int(res['pixels'][0])} pixels, gain {float(res['gain'][0]):.4f}, bias {float(res['bias'][0]):.3f}")
                     for r in range(3):
                         print("H " + " ".join("%.9g" % float(v) for v in model["h"][3 * r:3 * r + 3]))
                 if args.warp:   # no winner: the all-zero model covers nothing, the picture is black

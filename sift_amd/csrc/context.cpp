@@ -25,6 +25,7 @@
 #include "composite_kernels.h"
 #include "twoband_kernels.h"
 #include "overlap_kernels.h"
+#include "align_kernels.h"
 
 using namespace sift_hip;
 
@@ -216,6 +217,7 @@ struct sift_hip_ctx {
     sift_hip::CompositeState* composite_state = nullptr;   // the same for the compositor (composite.cpp)
     sift_hip::TwobandState* twoband_state = nullptr;       // the same for the two-band compositor (twoband.cpp)
     sift_hip::OverlapState* overlap_state = nullptr;       // and for the overlap statistics (overlap.cpp)
+    sift_hip::AlignScratch* align_state = nullptr;         // and for the direct alignment (align.cpp)
     // sub-pixel localisation (sift_hip_result_localize): the records and their (x, y) of the last batch, the images' row offsets
     DevBuf d_loc, d_loc_xy, d_loc_row0;
     HostBuf h_loc_row0;               // page-locked image of the row offsets (every call ends in a wait, so it is free again)
@@ -1310,6 +1312,7 @@ WarpState** warp_ctx_state(sift_hip_ctx* c) { return &c->warp_state; }
 CompositeState** composite_ctx_state(sift_hip_ctx* c) { return &c->composite_state; }
 TwobandState** twoband_ctx_state(sift_hip_ctx* c) { return &c->twoband_state; }
 OverlapState** overlap_ctx_state(sift_hip_ctx* c) { return &c->overlap_state; }
+AlignScratch** align_ctx_state(sift_hip_ctx* c) { return &c->align_state; }
 bool ransac_ctx_subpixel(sift_hip_ctx* c) { return c->plan.params.subpixel != 0; }
 const float* localize_ctx_xy(sift_hip_ctx* c) { return (c->have_result && c->loc_use) ? c->d_loc_xy.as<float>() : nullptr; }
 }  // namespace sift_hip
@@ -1365,6 +1368,7 @@ int sift_hip_create(int device, sift_hip_ctx** out, char* err, int errlen) {
                 tu_touch_composite(c->stream);
                 tu_touch_twoband(c->stream);
                 tu_touch_overlap(c->stream);
+                tu_touch_align(c->stream);
                 SIFT_HIP_CHECK(hipGetLastError());
                 SIFT_HIP_CHECK(hipStreamSynchronize(c->stream));
                 touched[device] = true;
@@ -1386,6 +1390,7 @@ void sift_hip_destroy(sift_hip_ctx* c) {
     composite_state_free(c->composite_state);
     twoband_state_free(c->twoband_state);
     overlap_state_free(c->overlap_state);
+    align_state_free(c->align_state);
     ApiGuard api;
     for (DevBuf* b : {&c->arena, &c->d_plan, &c->d_taps, &c->d_luts, &c->d_taps16, &c->d_input, &c->d_input_u8, &c->d_sparse_rec, &c->d_sparse_val, &c->d_base, &c->d_tmp, &c->d_tmp2,
                       &c->d_wk, &c->d_wi, &c->d_wi2, &c->d_wp, &c->d_status, &c->d_pool, &c->d_order, &c->d_masks, &c->d_fmasks, &c->d_counts, &c->d_tile_counts, &c->d_totals, &c->d_cands, &c->d_flags, &c->d_list, &c->d_list_cnt, &c->d_orient,

@@ -770,3 +770,40 @@ void hostmath_composite_twoband(const float* imgs, int w, int h, int n_canvases,
     }
 }
 }
+
+// ---- direct alignment (align_math.h): the plain loop ---------------------------------------------------------------
+#include "align_math.h"
+
+extern "C" {
+// the 80 sums of one pair (q, t) of imgs at (h, gain, bias): align_pair_sums
+void hostmath_align_sums(const float* imgs, int w, int h, int q, int t, const float* model, float gain, float bias, int border, double* sums) {
+    using namespace sift_hip;
+    const size_t frame = (size_t)w * (size_t)h;
+    std::vector<double> work((size_t)kAlignLanes * kAlignRec);
+    float m[9];
+    for (int k = 0; k < 9; ++k) m[k] = model[k];
+    align_pair_sums(imgs + (size_t)q * frame, imgs + (size_t)t * frame, w, h, m, gain, bias, border, align_norm(w, h), work.data(), sums);
+}
+
+// sift_hip_align_homography on the host: models in and out, out and sums (may be null: n_pairs x 80 doubles of each pair's last pass)
+void hostmath_align_homography(const float* imgs, int w, int h, int n_pairs, const int32_t* pair_q, const int32_t* pair_t, const sift_hip_align_params* p,
+                               sift_hip_homography* models, sift_hip_alignment* out, double* sums) {
+    using namespace sift_hip;
+    const size_t frame = (size_t)w * (size_t)h;
+    const AlignNorm nm = align_norm(w, h);
+    std::vector<double> work((size_t)kAlignLanes * kAlignRec);
+    for (int pair = 0; pair < n_pairs; ++pair) {
+        AlignState st;
+        align_begin(models[pair], st);
+        double S[kAlignRec] = {0.0}, M[kAlignUnknowns * kAlignStride];
+        for (int k = 0; k <= p->rounds && st.active; ++k) {
+            align_pair_sums(imgs + (size_t)pair_q[pair] * frame, imgs + (size_t)pair_t[pair] * frame, w, h, st.h, st.a, st.b, p->border, nm, work.data(), S);
+            align_round(st, S, k, p->rounds, p->min_pixels, (double)p->damping, nm, M);
+        }
+        align_result(st, out[pair]);
+        for (int i = 0; i < 9; ++i) models[pair].h[i] = st.acc_h[i];
+        if (sums)
+            for (int e = 0; e < kAlignRec; ++e) sums[(size_t)pair * kAlignRec + e] = S[e];
+    }
+}
+}

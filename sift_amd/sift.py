@@ -913,6 +913,47 @@ class Context:
         got = (res,) + ((msk,) if msk is not None else ()) + (((int(tiles[0]), int(tiles[1])),) if want_tiles else ())
         return got[0] if len(got) == 1 else got
 
+    # ---- direct alignment (include/sift_hip.h, "direct alignment") ----------------------------------------------
+    def align_homography(self, imgs, pairs, models, rounds=4, border=2, min_pixels=256, damping=0.0, path=0, out=None, want_sums=False, shape=None):
+        """sift_hip_align_homography: refines models[p] (query to train) of pair p = (query, train) on the pixels of the two
+        frames, by at most `rounds` (0 .. 8) Gauss-Newton steps on sum (Q - gain T(H .) - bias)^2 -> (models, out[, sums]):
+        the records with h rewritten, and one ALIGNMENT_DTYPE record per pair (h, gain, bias, rms0, rms, pixels, rounds,
+        status).  `imgs`: a numpy array [n, h, w], or a tensor / an address (device memory) with `shape` = (n, h, w);
+        `models`: HOMOGRAPHY_DTYPE records (copied; [n_pairs, 9] numbers become records with iteration 0), or a tensor / an
+        address of such records (host or device memory), rewritten in place; `out`: where the result records go (returned as given);
+        `border`: pixels of the query frame's rim left out; a pass with fewer than `min_pixels` pixels stops its pair;
+        `damping`: the diagonal of the normal matrix times 1 + damping; `path` 1: the masked kernel (the same bits);
+        `want_sums`: [n_pairs, 80] float64, the sums of each pair's last pass."""
+        if isinstance(imgs, np.ndarray):
+            imgs = np.ascontiguousarray(imgs, np.float32)
+            imgs = imgs[None] if imgs.ndim == 2 else imgs
+            shape = imgs.shape
+        elif shape is None:
+            shape = tuple(imgs.shape)   # a tensor
+        if len(shape) != 3:
+            raise ValueError("align_homography: imgs is [n, h, w]")
+        if not 0 <= int(path) <= 255:
+            raise ValueError("align_homography: path must be 0 or 1")
+        pq, pt = self._pairs(pairs)
+        if isinstance(models, (np.ndarray, list, tuple)):
+            if isinstance(models, np.ndarray) and models.dtype.names:
+                models = np.array(models, _lib.HOMOGRAPHY_DTYPE).reshape(-1)
+            else:
+                h9 = np.ascontiguousarray(models, np.float32).reshape(-1, 9)
+                models = np.zeros(h9.shape[0], _lib.HOMOGRAPHY_DTYPE)
+                models["h"] = h9
+            if models.size != pq.size:
+                raise ValueError("align_homography: one model per pair")
+        res = np.zeros(pq.size, _lib.ALIGNMENT_DTYPE) if out is None else out
+        sums = np.zeros((pq.size, _lib.ALIGN_SUMS), np.float64) if want_sums else None
+        prm = _lib.AlignParams(int(rounds), int(border), int(min_pixels), float(damping), int(path))
+        err = C.create_string_buffer(512)
+        rc = self._L.sift_hip_align_homography(self._h, self._addr(imgs), int(shape[0]), int(shape[2]), int(shape[1]), pq.size, pq, pt, C.byref(prm),
+                                               self._addr(models), self._addr(res), self._addr(sums), err, 512)
+        if rc:
+            _raise(rc, err)
+        return (models, res, sums) if want_sums else (models, res)
+
     # ---- compositor (include/sift_hip.h, "compositor") ---------------------------------------------------------
     @staticmethod
     def _composite_inputs(name, imgs, models, offsets, src, out_shape, interp, shape, gains):
@@ -1288,11 +1329,12 @@ class Sift:
         return recs, models[0], inlier
 
     def register(self, imgs, pairs, ratio: float = 0.8, cross_check: bool = False, iterations: int = 2048, threshold: float = 3.0, seed: int = 0,
-                 refine: int = 0, quantized: bool = False, fill: float = 0.0, interp: str = "bilinear"):
+                 refine: int = 0, quantized: bool = False, fill: float = 0.0, interp: str = "bilinear", align: int = 0):
         """Registration (an extension): calculate() on every frame of `imgs` [n, h, w], verify() on every pair (query, train) and
         Context.warp_homography of each pair's train frame into its query frame -> (models, registered, mask): one homography
         record per pair, registered[p] the train frame resampled on the query frame's pixels, mask[p] 1 where it is covered
-        (elsewhere `fill`; a pair without a model is all `fill`).  Bit for bit the composition of those calls."""
+        (elsewhere `fill`; a pair without a model is all `fill`).  Bit for bit the composition of those calls.  `align` > 0:
+        Context.align_homography(rounds=align) refines every pair's model on the pixels before the warp."""
         imgs = np.asarray(imgs)
         if imgs.ndim != 3:
             raise ValueError("register: imgs is [n, h, w]")
@@ -1301,6 +1343,8 @@ class Sift:
         models = np.zeros(len(pairs), _lib.HOMOGRAPHY_DTYPE)
         for p, (q, t) in enumerate(pairs):
             models[p] = self.verify(points[q], points[t], ratio, cross_check, iterations, threshold, seed, refine, "homography", quantized)[1]
+        if align:
+            models = self.ctx.align_homography(imgs.astype(np.float32), pairs, models, rounds=align)[0]
         registered, mask = self.ctx.warp_homography(imgs.astype(np.float32), models, [t for _, t in pairs], fill=fill, interp=interp, mask=True)
         return models, registered, mask
 
@@ -1326,7 +1370,7 @@ class Sift:
 
     def mosaic(self, imgs, ref: int = 0, pairs=None, blend: str = "feather", ratio: float = 0.8, cross_check: bool = False, iterations: int = 2048,
                threshold: float = 3.0, seed: int = 0, refine: int = 0, quantized: bool = False, fill: float = 0.0, interp: str = "bilinear",
-               chain: bool = False, canvas=None, gain: bool = False, scale: float = 1.0, band_sigma: float = 5.0):
+               chain: bool = False, canvas=None, gain: bool = False, scale: float = 1.0, band_sigma: float = 5.0, align: int = 0):
         """A mosaic or a stack (an extension): calculate() on every frame of `imgs` [n, h, w], verify() on every pair (query,
         train) and Context.composite_homography of the placed frames on one canvas in frame `ref`'s coordinates -> (models,
         canvas, count, origin): one homography record per pair, the picture [out_h, out_w], the number of frames that cover each
@@ -1339,7 +1383,9 @@ class Sift:
         shape) = ((x, y), (out_h, out_w)).  Bit for bit the composition of those calls.  `gain`: Context.overlap_stats(gains=True, scale=`scale`)
         on the same canvas first, the gains given to the compositor -> (models, canvas, count, origin, gains, zncc): one gain
         per placed frame in job order and Context.overlap_zncc of the placed frames (at most 32).  `blend` "twoband":
-        Context.composite_twoband(sigma=`band_sigma`) in the compositor's place, also together with `gain`."""
+        Context.composite_twoband(sigma=`band_sigma`) in the compositor's place, also together with `gain`.  `align` > 0:
+        Context.align_homography(rounds=align) refines every pair's model on the pixels of its two frames before the chain
+        product and the choice of the canvas."""
         imgs = np.asarray(imgs)
         if imgs.ndim != 3:
             raise ValueError("mosaic: imgs is [n, h, w]")
@@ -1355,6 +1401,9 @@ class Sift:
         job_models, src = [np.eye(3, dtype=np.float32).reshape(9)], [ref]
         for p, (q, t) in enumerate(pairs):
             models[p] = self.verify(points[q], points[t], ratio, cross_check, iterations, threshold, seed, refine, "homography", quantized)[1]
+        if align:
+            models = self.ctx.align_homography(imgs.astype(np.float32), pairs, models, rounds=align)[0]
+        for p, (q, t) in enumerate(pairs):
             if models[p]["iteration"] < 0 or q not in to_ref or t in to_ref:
                 continue
             to_ref[t] = models[p]["h"].astype(np.float64).reshape(3, 3) @ to_ref[q]
